@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric on MI355X: images/sec of a SLaK-T 51x51, 224 px, bf16 TRAIN STEP
-(forward + loss + backward + AdamW step) with every depthwise conv running the hand-written HIP kernels,
-plus the HBM roofline of the dominant hot-path kernel and the reference CPU nn.Conv2d path timed beside it.
+(forward + loss + backward + AdamW step) with every depthwise conv running the hand-written HIP kernels.
+A plain run sets up, warms up, times the K steps and prints the result line; `--full` adds, after the timed steps, the HBM roofline of
+the dominant hot-path kernel, the Masking kernels alone and the reference CPU nn.Conv2d path timed beside it.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
@@ -14,7 +15,7 @@ RCCL, SyncBN, Masking sparsity 0.4 with prune-and-grow every 2000 steps), weak s
 The other BASELINE configurations run with the same command and the same JSON line:
     python bench.py --model base                      configs[3]: SLaK-B 51x51, 64 images per GPU (512 over 8), sparsity 0.4
     python bench.py --kernel 61 --res 384             configs[4]: SLaK-T 61x61 at 384 px, 64 images per GPU (256 over 4)
-`mask_step` (rank 0, outside the timed region): the Masking kernels alone on the model's mask set -- apply and prune-and-grow,
+`mask_step` (--full, rank 0, outside the timed region): the Masking kernels alone on the model's mask set -- apply and prune-and-grow,
 HIP-event timed, against SURVEY 8(d)'s 12 / 20 bytes per masked element -- next to a CPU port of the reference step.
 """
 import argparse
@@ -129,7 +130,34 @@ def parse():
     ap.add_argument("--ddp-reference-flags", action="store_true", help="N>1: DistributedDataParallel exactly as main.py:374-376 constructs it (broadcast_buffers and "
                     "gradient_as_bucket_view at their defaults); default: broadcast_buffers=False, gradient_as_bucket_view=True, the stock all-reduce comm hook (same results, less host time, one copy and 312 tiny launches less)")
     ap.add_argument("--per-step-sync", action="store_true", help="torch.cuda.synchronize() after every step, as engine.py:90 does (default: the K steps are only bracketed)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure what the headline figure does not need: the host's enqueue cost on a drained queue "
+                    "(config.host_enqueue_ms_per_step), the dw-conv launches one by one (`roofline`, `hot_path`), the Masking kernels (`mask_step`) and the CPU reference "
+                    "(`cpu_baseline`); --no-roofline / --no-mask-bench / --no-cpu-baseline take single legs out again.  Without it those keys are absent (the host figure: null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="rank 0 writes what the LAST timed step computed as DIR/<name>.npy (float32 / float64, under 2 MB in all): loss, logits, "
+                    "and of the parameters that step left behind a fixed seeded sample (params_sample) and every tensor's l2 norm (param_norms).  Inputs and "
+                    "initial weights are seeded, so two builds run with the same arguments can be compared output for output")
     return ap.parse_args()
+
+
+DUMP_SAMPLE_PER_TENSOR = 2048   # --dump-outputs: elements taken of every parameter tensor (all of a smaller one), at indices drawn once from a seeded generator
+
+
+def dump_outputs(path, loss, logits, model):
+    """--dump-outputs: the arrays a caller of the train step holds after the last timed step.  Parameters are visited in named_parameters() order (the DDP
+    wrapper's `module.` prefix does not change it); the sample indices depend on that order and the tensor sizes only."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(20240229)
+    sample, norms = [], []
+    for _, p in model.named_parameters():
+        flat = p.detach().float().reshape(-1).cpu().numpy()
+        norms.append(np.sqrt(np.sum(flat.astype(np.float64) ** 2)))
+        sample.append(flat if flat.size <= DUMP_SAMPLE_PER_TENSOR else flat[rng.integers(0, flat.size, DUMP_SAMPLE_PER_TENSOR)])
+    arrays = {"loss": np.asarray([float(loss)], dtype=np.float64), "logits": logits.detach().float().cpu().numpy(),
+              "params_sample": np.concatenate(sample).astype(np.float32), "param_norms": np.asarray(norms, dtype=np.float64)}
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+    return {name: list(arr.shape) for name, arr in arrays.items()}
 
 
 def event_time_ms(fn, reps, stream_device):
@@ -547,9 +575,14 @@ def main():
         with torch.autocast("cuda", dtype=torch.bfloat16, cache_enabled=False):
             fwd = torch.cuda.make_graphed_callables(model, (samples,), num_warmup_iters=3)
 
+    last = {}                                                     # --dump-outputs: the logits of the most recent step (a reference, no copy, no sync)
+
     def step():
         with torch.autocast("cuda", dtype=torch.bfloat16, cache_enabled=not a.graph):
-            loss = criterion(fwd(samples), targets)
+            logits = fwd(samples)
+            loss = criterion(logits, targets)
+        if a.dump_outputs:
+            last["logits"] = logits
         loss.backward()
         if mask is not None:
             mask.step()                                           # engine.py:82-83
@@ -585,15 +618,18 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    dumped = None
+    if a.dump_outputs and rank == 0 and a.steps > 0:              # before anything below steps the model again: what the LAST TIMED step computed
+        dumped = dump_outputs(a.dump_outputs, loss.item(), last["logits"], model)
     # The K timed steps above enqueue faster than the GPU executes: after a few steps the runtime's launch queue is full and every further launch
     # WAITS for the GPU, so `host_s` tends to the GPU's step time whatever the host costs.  The host's own cost per step: three steps enqueued
-    # on a drained queue (nothing to wait for), synchronised afterwards.
-    host_free_s = float("inf")                                    # (three rounds, the quietest one: a drained-queue round of 3 steps is easily disturbed)
-    for _ in range(3):
+    # on a drained queue (nothing to wait for), synchronised afterwards.  (--full only: nine more steps that the headline figure does not need)
+    host_free_s = None
+    for _ in range(3 if a.full else 0):                           # (three rounds, the quietest one: a drained-queue round of 3 steps is easily disturbed)
         h0 = time.perf_counter()
         for _ in range(3):
             step()
-        host_free_s = min(host_free_s, (time.perf_counter() - h0) / 3)
+        host_free_s = min(host_free_s or float("inf"), (time.perf_counter() - h0) / 3)
         torch.cuda.synchronize()
     if a.host_profile:                                            # after the timed region: where the enqueue time goes
         import cProfile, pstats
@@ -667,13 +703,15 @@ def main():
                    "hip_graph": ("forward and backward of the model replayed as two captured HIP graphs (torch.cuda.make_graphed_callables)" if a.graph else None),
                    "timing": "K steps between barrier + torch.cuda.synchronize() on both sides; " + ("a synchronize after every step as engine.py:90" if a.per_step_sync else "no synchronize inside (GPU-busy time == step time: the host runs ahead)"),
                    "per_rank_ms_per_step": [round(v, 4) for v in per_rank_ms],
-                   "host_enqueue_ms_per_step": round(1e3 * host_free_s, 3),
+                   "host_enqueue_ms_per_step": (None if host_free_s is None else round(1e3 * host_free_s, 3)),   # measured under --full only
+                   "full": bool(a.full), "dumped_outputs": dumped,
                    "host_enqueue_ms_per_step_in_timed_region": round(1e3 * host_s / a.steps, 3),
                    "mask_sync": mask_sync,
                    "final_loss": final_loss},
     }
 
-    if rank == 0 and not a.no_roofline:
+    # ---- everything below takes runs of its own and is not part of the headline figure: --full only
+    if a.full and rank == 0 and not a.no_roofline:
         del samples
         torch.cuda.empty_cache()
         kl = hot_path_kernels(device, a.batch, a.kernel_reps, torch.float32 if a.fp32_dwconv else torch.bfloat16, stages)
@@ -717,12 +755,12 @@ def main():
                            "share_of_step": hot_ms / ms_per_step,
                            "images_per_s_dwconv_only": a.batch / (hot_ms / 1e3),
                            "kernels": [{k2: (round(v, 4) if isinstance(v, float) else v) for k2, v in k.items()} for k in kl]}
-    if rank == 0 and not a.no_mask_bench:
+    if a.full and rank == 0 and not a.no_mask_bench:
         out["mask_step"] = mask_step_bench(device, a.model, ks, a.only_L)
         if "roofline" in out:
             out["roofline"]["mask_apply_frac"] = out["mask_step"]["apply_frac_of_hbm_peak"]
             out["roofline"]["mask_update_frac"] = out["mask_step"]["update_frac_of_hbm_peak"]
-    if rank == 0 and n_gpus == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and n_gpus == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(min(os.cpu_count() or 1, 32), stages, label)   # >32 threads only oversubscribes a 96-channel depthwise conv
     if rank == 0:
         try:                                                        # text that C libraries left in the C stdio buffer (RCCL's NCCL_DEBUG=VERSION banner) goes out FIRST,

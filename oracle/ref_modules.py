@@ -6,8 +6,9 @@ The two files that sit directly on the drop-in boundary are Python:
     reference_models_SLaK           = /root/reference/models/SLaK.py
 
 /root/reference does not exist on the GPU box, and reference SOURCES are never copied into the repository.  What travels is the
-same thing that travels for a compiled reference: a BUILD OUTPUT under ``oracle/_ref/`` (git-ignored, not gpurun-ignored) -- here
-CPython bytecode made by ``py_compile`` from the files where they lie (``build()``, called by ``__graft_entry__.build()`` whenever
+same thing that travels for a compiled reference: a BUILD OUTPUT under ``oracle/_ref/`` (git-ignored) -- here CPython bytecode in
+``<name>.bytecode`` files (a build product the tests need, so not named like an interpreter cache, which file transfers and cleaners
+drop) made by ``py_compile`` from the files where they lie (``build()``, called by ``__graft_entry__.build()`` whenever
 /root/reference is present).  ``load()`` returns the module from the source when the checkout is there and from the bytecode
 otherwise, so ``-m gpu`` tests run the UNMODIFIED reference modules on top of ``libslak_hip.so`` on the GPU box.
 
@@ -38,8 +39,11 @@ SOURCES = {
 }
 
 
+BYTECODE_SUFFIX = ".bytecode"   # not ".pyc": whatever copies a tree without its Python caches would leave these build products behind
+
+
 def pyc_path(name):
-    return os.path.join(OUT, name + ".pyc")
+    return os.path.join(OUT, name + BYTECODE_SUFFIX)
 
 
 def build():

@@ -33,7 +33,7 @@ sys.path.insert(0, GOLDEN)
 def _engine():
     from oracle import ref_modules
     if not (ref_modules.available("reference_engine") and ref_modules.available("reference_utils")):
-        pytest.fail("oracle/_ref/reference_engine.pyc is missing: run __graft_entry__.build() in the build container")
+        pytest.fail("oracle/_ref/reference_engine" + ref_modules.BYTECODE_SUFFIX + " is missing: run __graft_entry__.build() in the build container")
     return ref_modules.load_engine()
 
 

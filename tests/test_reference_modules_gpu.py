@@ -25,7 +25,7 @@ LIBDIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))
 def _ref_modules():
     from oracle import ref_modules
     for n in ref_modules.SOURCES:
-        assert ref_modules.available(n), "run __graft_entry__.build() where /root/reference exists: oracle/_ref/%s.pyc missing" % n
+        assert ref_modules.available(n), "run __graft_entry__.build() where the reference checkout exists: oracle/_ref/%s%s missing" % (n, ref_modules.BYTECODE_SUFFIX)
     return ref_modules
 
 
@@ -44,7 +44,7 @@ def test_reference_bytecode_is_built_and_loads(force_bytecode, monkeypatch):
         rm.build()
         monkeypatch.setattr(rm, "FORCE_BYTECODE", True)
     op = rm.load_dwconv_module(_pybind_ready())
-    assert op.__spec__.origin.endswith(".pyc") == (force_bytecode or not os.path.isdir(rm.REF))
+    assert op.__spec__.origin.endswith(rm.BYTECODE_SUFFIX) == (force_bytecode or not os.path.isdir(rm.REF))
     assert op.__all__ == ["DepthWiseConv2dImplicitGEMM"]
     m = op.DepthWiseConv2dImplicitGEMM(6, (51, 5), bias=False)
     assert isinstance(m, torch.nn.Conv2d) and tuple(m.weight.shape) == (6, 1, 51, 5) and m.padding == (0, 0)

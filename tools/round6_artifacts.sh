@@ -4,23 +4,23 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r06; mkdir -p $O
 cd $R
 git rev-parse HEAD > $O/commit.txt 2>/dev/null
 Q="--steps 20 --warmup 5 --no-cpu-baseline --no-mask-bench"
-timeout 900 python bench.py                                                          2> $O/bench_cfg1.err | tail -1 > $O/bench_cfg1.json
-timeout 600 python bench.py --sparsity 0.4 --no-cpu-baseline --no-mask-bench          2>/dev/null | tail -1 > $O/bench_cfg2_sparsity04.json
-timeout 600 python bench.py --model base $Q                                           2>/dev/null | tail -1 > $O/bench_cfg3_slak_b.json
-timeout 600 python bench.py --kernel 61 --res 384 $Q                                  2>/dev/null | tail -1 > $O/bench_cfg4_61x61_384px.json
-SLAK_WIDE_TRI=0 timeout 600 python bench.py --kernel 61 --res 384 $Q --no-roofline    2>/dev/null | tail -1 > $O/bench_cfg4_wide_tri_off.json
-SLAK_TRI_ROWS_SD=0 timeout 600 python bench.py $Q --no-roofline                       2>/dev/null | tail -1 > $O/bench_cfg1_tri_rows_sd_off.json
-timeout 600 python bench.py --fp32-dwconv --no-cpu-baseline --no-mask-bench --no-roofline 2>/dev/null | tail -1 > $O/bench_fp32_dwconv_exact.json
+timeout 900 python bench.py --full                                                          2> $O/bench_cfg1.err | tail -1 > $O/bench_cfg1.json
+timeout 600 python bench.py --full --sparsity 0.4 --no-cpu-baseline --no-mask-bench          2>/dev/null | tail -1 > $O/bench_cfg2_sparsity04.json
+timeout 600 python bench.py --full --model base $Q                                           2>/dev/null | tail -1 > $O/bench_cfg3_slak_b.json
+timeout 600 python bench.py --full --kernel 61 --res 384 $Q                                  2>/dev/null | tail -1 > $O/bench_cfg4_61x61_384px.json
+SLAK_WIDE_TRI=0 timeout 600 python bench.py --full --kernel 61 --res 384 $Q --no-roofline    2>/dev/null | tail -1 > $O/bench_cfg4_wide_tri_off.json
+SLAK_TRI_ROWS_SD=0 timeout 600 python bench.py --full $Q --no-roofline                       2>/dev/null | tail -1 > $O/bench_cfg1_tri_rows_sd_off.json
+timeout 600 python bench.py --full --fp32-dwconv --no-cpu-baseline --no-mask-bench --no-roofline 2>/dev/null | tail -1 > $O/bench_fp32_dwconv_exact.json
 # the N > 1 code path on one GPU over RCCL (world size 1), SLaK-T and SLaK-B, with main.py:374-376's own constructor flags beside it
 D="$Q --no-roofline --force-dist"
-timeout 600 python bench.py $D --sparsity 0.4                                         2>/dev/null | grep '^{' | tail -1 > $O/bench_nccl_ws1.json
-timeout 600 python bench.py $D --sparsity 0.4 --ddp-reference-flags                   2>/dev/null | grep '^{' | tail -1 > $O/bench_nccl_ws1_ddp_reference_flags.json
-SLAK_GRAD_SLOTS=0 timeout 600 python bench.py $D --sparsity 0.4                       2>/dev/null | grep '^{' | tail -1 > $O/bench_nccl_ws1_no_grad_slots.json
-SLAK_BN_BWD_ASYNC=1 timeout 600 python bench.py $D --sparsity 0.4                     2>/dev/null | grep '^{' | tail -1 > $O/bench_nccl_ws1_bn_bwd_async.json
-SLAK_FORCE_BN_EXCHANGE=0 timeout 600 python bench.py $D --sparsity 0.4                2>/dev/null | grep '^{' | tail -1 > $O/bench_nccl_ws1_ddp_only.json
-timeout 600 python bench.py $D --model base                                           2>/dev/null | grep '^{' | tail -1 > $O/bench_nccl_ws1_slak_b.json
-timeout 600 python bench.py $D --model base --ddp-reference-flags                     2>/dev/null | grep '^{' | tail -1 > $O/bench_nccl_ws1_slak_b_ddp_reference_flags.json
-SLAK_TUNED_GEMMS=0 OMP_NUM_THREADS=4 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --backend gloo --device 0 --steps 5 --warmup 2 --prime 2 --batch 32 --no-roofline --no-mask-bench --no-cpu-baseline 2>/dev/null | grep '^{' | tail -1 > $O/bench_n2_two_ranks_one_gpu_gloo.json
+timeout 600 python bench.py --full $D --sparsity 0.4                                         2>/dev/null | grep '^{' | tail -1 > $O/bench_nccl_ws1.json
+timeout 600 python bench.py --full $D --sparsity 0.4 --ddp-reference-flags                   2>/dev/null | grep '^{' | tail -1 > $O/bench_nccl_ws1_ddp_reference_flags.json
+SLAK_GRAD_SLOTS=0 timeout 600 python bench.py --full $D --sparsity 0.4                       2>/dev/null | grep '^{' | tail -1 > $O/bench_nccl_ws1_no_grad_slots.json
+SLAK_BN_BWD_ASYNC=1 timeout 600 python bench.py --full $D --sparsity 0.4                     2>/dev/null | grep '^{' | tail -1 > $O/bench_nccl_ws1_bn_bwd_async.json
+SLAK_FORCE_BN_EXCHANGE=0 timeout 600 python bench.py --full $D --sparsity 0.4                2>/dev/null | grep '^{' | tail -1 > $O/bench_nccl_ws1_ddp_only.json
+timeout 600 python bench.py --full $D --model base                                           2>/dev/null | grep '^{' | tail -1 > $O/bench_nccl_ws1_slak_b.json
+timeout 600 python bench.py --full $D --model base --ddp-reference-flags                     2>/dev/null | grep '^{' | tail -1 > $O/bench_nccl_ws1_slak_b_ddp_reference_flags.json
+SLAK_TUNED_GEMMS=0 OMP_NUM_THREADS=4 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --backend gloo --device 0 --steps 5 --warmup 2 --prime 2 --batch 32 --no-roofline --no-mask-bench --no-cpu-baseline 2>/dev/null | grep '^{' | tail -1 > $O/bench_n2_two_ranks_one_gpu_gloo.json
 # the step under the profiler: N = 1 and the N > 1 path
 BENCH_ARGS="--no-mask-bench" timeout 600 bash tools/profile_bench.sh > /dev/null 2>&1
 cp gpurun_out/sum/bench_kernel_stats.txt $O/bench_kernel_stats.txt; cp gpurun_out/sum/step_breakdown.txt $O/step_breakdown.txt; cp gpurun_out/sum/bench_under_rocprof.json $O/bench_under_rocprof.json
