@@ -239,6 +239,26 @@ int slak_scale_residual_backward(const float* dout, const void* dout_bf16, float
                                  const float* sample_scale, void* dz_bf16, float* dgamma, float* dz_colsum, int N, int C, int P,
                                  void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same four ops with a row pitch on the NHWC side (`--width_factor 1.3`: C = 124 / 249 / 499 / 998).  The NCHW tensors (x, dx, shortcut,
+ * out, dout) keep their logical C; y, g, z, dz are (N,H,W,ldc) contiguous, i.e. rows of ldc >= C elements.  1 <= C <= 1024 of ANY parity,
+ * ldc % 8 == 0, ldc <= 1024, else SLAK_ERR_UNSUPPORTED; workspace >= slak_block_tail_workspace_bytes(N, ldc, P).  Arguments as the plain entry
+ * points, ldc last.
+ *   - the LayerNorm statistics and every 1/C factor use the logical C; columns c >= C never enter a sum;
+ *   - columns c >= C of y and of dz are WRITTEN, as +0.0, on every call (the next GEMM reads whole rows);
+ *   - columns c >= C of g and z are never used: they may hold anything, NaN included;
+ *   - weight, bias, gamma, dweight, dbias, dgamma, dz_colsum are [C].
+ * ldc == C (then C % 8 == 0) forwards to the plain entry point: the same bits. */
+int slak_ln_nchw_to_nhwc_forward_ld(const void* x_bf16, const float* weight, const float* bias, void* y_bf16, float* mean, float* rstd,
+                                    int N, int C, int P, float eps, void* stream, int ldc);
+int slak_ln_nchw_to_nhwc_backward_ld(const void* g_bf16, const void* x_bf16, const float* weight, const float* mean, const float* rstd,
+                                     void* dx_bf16, float* dweight, float* dbias, int N, int C, int P,
+                                     void* workspace, size_t workspace_bytes, void* stream, int ldc);
+int slak_scale_residual_forward_ld(const void* shortcut, int shortcut_dtype, const void* z_bf16, const float* gamma, const float* sample_scale,
+                                   float* out, void* out_bf16, int N, int C, int P, void* stream, int ldc);
+int slak_scale_residual_backward_ld(const float* dout, const void* dout_bf16, float* dout_sum, const void* z_bf16, const float* gamma,
+                                    const float* sample_scale, void* dz_bf16, float* dgamma, float* dz_colsum, int N, int C, int P,
+                                    void* workspace, size_t workspace_bytes, void* stream, int ldc);
+
 /* Downsample layers (models/SLaK.py:285-311: LayerNorm(C, data_format="channels_first") -> Conv2d(C, C', kernel_size=2, stride=2)).  The
  * kernel/stride-2 convolution is a GEMM on non-overlapping 2x2 patches; slak_ln_patch_forward normalises the fp32 NCHW input over C and
  * writes the result (rounded to bf16, as autocast's cast in front of the conv does) directly as that GEMM's operand
@@ -356,6 +376,13 @@ int slak_linear_gemm(const void* a_bf16, const void* b_bf16, const void* bias_bf
  * pointers): the pointwise weights as the data-gradient GEMMs read them (dz . W2, dy1 . W1: models/SLaK.py:158-160 backwards).  Replaces one strided copy
  * kernel per weight, block and step (25 launches per SLaK-T step) by one launch per optimizer step (slak_amd/block_ops.lowp_param_t caches by version). */
 int slak_transpose_bf16_batch(const void* const* src, void* const* dst, const int* rows, const int* cols, int n, void* stream);
+
+/* Zero-padded bf16 copies of n fp32 matrices src[i] [rows][cols] in ONE launch (host arrays of device pointers; any rows / cols, source rows need
+ * only the 4-byte alignment of a float): dst[i] is [dst_rows][dst_cols] bf16 with dst = bf16(src) in its upper left corner (transpose[i] == 0;
+ * dst_rows >= rows, dst_cols >= cols) or dst = bf16(src)^T there (transpose[i] != 0; dst_rows >= cols, dst_cols >= rows) and +0.0 everywhere else.
+ * The weights and biases of a block whose NHWC tensors carry a row pitch (slak_*_ld above) as its GEMMs read them. */
+int slak_pad_cast_bf16_batch(const void* const* src_f32, void* const* dst_bf16, const int* rows, const int* cols, const int* dst_rows,
+                             const int* dst_cols, const int* transpose, int n, void* stream);
 
 /* Weight gradient of the pointwise Linear layers (models/SLaK.py:117-118 pwconv1 / pwconv2; autograd's dW = dY^T X):
  * d[N1][N2] (fp32) = x1^T x2 over the M rows of x1 [M][N1] and x2 [M][N2] (bf16, row-major), fp32 accumulate, summed in a fixed

@@ -21,9 +21,36 @@ def _chk(t, name, dtype=None):
         raise TypeError("%s must be %s, got %s" % (name, dtype, t.dtype))
 
 
-def _ln_fwd_impl(x, weight, bias, eps):
+pad_even_widths = os.environ.get("SLAK_PAD_EVEN", "0") == "1"     # also pad the even widths that are no multiple of 32 (124 -> 128, 998 -> 1024): aligned GEMM rows at width 1.3
+pitched_block_hits = 0                                             # block tails / whole blocks that ran on pitched NHWC tensors so far (tests, tools/time_width.py)
+
+
+def nhwc_pitch(C):
+    """Row pitch (elements) of a block's NHWC intermediates for C channels, or None where the fused tail does not exist (C > 1024).
+    Even C: C itself -- the launches and bits of the plain entry points (with ``pad_even_widths``: the next multiple of 64 unless C % 32 == 0, so
+    the ConvNeXt widths 96 * 2^k and 128 * 2^k are never padded).  Odd C: the next multiple of 64; the pad columns hold zeros and the pointwise
+    GEMMs read zero-padded weight copies (padded_params)."""
+    C = int(C)
+    if C < 1 or C > 1024:
+        return None
+    if C % 2 == 0 and not (pad_even_widths and C % 32):
+        return C
+    return (C + 63) // 64 * 64
+
+
+def _ln_fwd_impl(x, weight, bias, eps, ldc=None):
+    """ldc: row pitch of y (None / C: the plain op).  Pitched: y is (N,H,W,ldc) with exact zeros in the columns c >= C."""
     _chk(x, "x", torch.bfloat16); _chk(weight, "weight", torch.float32); _chk(bias, "bias", torch.float32)
     N, C, H, W = x.shape
+    if ldc is not None and ldc != C:
+        y = torch.empty((N, H, W, ldc), dtype=torch.bfloat16, device=x.device)
+        mean = torch.empty((N, H * W), dtype=torch.float32, device=x.device)
+        rstd = torch.empty_like(mean)
+        with _on(x.device):
+            _lib.check(_lib.lib().slak_ln_nchw_to_nhwc_forward_ld(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), y.data_ptr(), mean.data_ptr(),
+                                                                  rstd.data_ptr(), N, C, H * W, float(eps), _stream(x.device), int(ldc)),
+                       "slak_ln_nchw_to_nhwc_forward_ld")
+        return y, mean, rstd
     y = torch.empty((N, H, W, C), dtype=torch.bfloat16, device=x.device)
     mean = torch.empty((N, H * W), dtype=torch.float32, device=x.device)
     rstd = torch.empty_like(mean)
@@ -53,6 +80,15 @@ def _ln_bwd_impl(g, x, weight, mean, rstd):
     dx = torch.empty_like(x)
     dw = torch.empty_like(weight); db = torch.empty_like(weight)
     L = _lib.lib()
+    ldc = g.shape[-1]
+    if ldc != C:                                       # pitched gradient (N,H,W,ldc): its columns c >= C are never read
+        ws, nb = _workspace(_tail_ws_bytes(N, ldc, H * W), x.device)
+        with _on(x.device):
+            _lib.check(L.slak_ln_nchw_to_nhwc_backward_ld(g.data_ptr(), x.data_ptr(), weight.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                                          dx.data_ptr(), dw.data_ptr(), db.data_ptr(), N, C, H * W,
+                                                          ws.data_ptr() if ws is not None else None, nb, _stream(x.device), ldc),
+                       "slak_ln_nchw_to_nhwc_backward_ld")
+        return dx, dw, db
     ws, nb = _workspace(_tail_ws_bytes(N, C, H * W), x.device)
     with _on(x.device):
         _lib.check(L.slak_ln_nchw_to_nhwc_backward(g.data_ptr(), x.data_ptr(), weight.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
@@ -63,8 +99,8 @@ def _ln_bwd_impl(g, x, weight, mean, rstd):
 
 class _LnNchwToNhwc(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, eps):
-        y, mean, rstd = _ln_fwd_impl(x, weight, bias, eps)
+    def forward(ctx, x, weight, bias, eps, ldc=None):
+        y, mean, rstd = _ln_fwd_impl(x, weight, bias, eps, ldc)
         ctx.save_for_backward(x, weight, mean, rstd)
         return y
 
@@ -72,20 +108,28 @@ class _LnNchwToNhwc(torch.autograd.Function):
     def backward(ctx, g):
         x, weight, mean, rstd = ctx.saved_tensors
         dx, dw, db = _ln_bwd_impl(g, x, weight, mean, rstd)
-        return dx, dw, db, None
+        return dx, dw, db, None, None
 
 
 def _scale_residual_fwd(shortcut, z, gamma, sample_scale, emit_lowp):
     _chk(shortcut, "shortcut"); _chk(z, "z", torch.bfloat16); _chk(gamma, "gamma", torch.float32)
     N, C, H, W = shortcut.shape
-    if z.shape != (N, H, W, C):
-        raise RuntimeError("z must be (N,H,W,C)")
+    ldc = z.shape[-1] if z.dim() == 4 else -1
+    if z.dim() != 4 or z.shape[:3] != (N, H, W) or ldc < C or (ldc != C and ldc % 8):
+        raise RuntimeError("z must be (N,H,W,C), or (N,H,W,ldc) with a row pitch ldc > C, ldc % 8 == 0")
     sdt = {torch.float32: _lib.SLAK_F32, torch.bfloat16: _lib.SLAK_BF16}.get(shortcut.dtype)
     if sdt is None:
         raise TypeError("shortcut must be float32 or bfloat16")
     out = torch.empty((N, C, H, W), dtype=torch.float32, device=z.device)
     out16 = torch.empty((N, C, H, W), dtype=torch.bfloat16, device=z.device) if emit_lowp else None
     L = _lib.lib()
+    if ldc != C:                                       # pitched z: its columns c >= C are never read
+        with _on(z.device):
+            _lib.check(L.slak_scale_residual_forward_ld(shortcut.data_ptr(), sdt, z.data_ptr(), gamma.data_ptr(),
+                                                        sample_scale.data_ptr() if sample_scale is not None else None,
+                                                        out.data_ptr(), out16.data_ptr() if emit_lowp else None,
+                                                        N, C, H * W, _stream(z.device), ldc), "slak_scale_residual_forward_ld")
+        return out, out16
     with _on(z.device):
         _lib.check(L.slak_scale_residual_forward(shortcut.data_ptr(), sdt, z.data_ptr(), gamma.data_ptr(),
                                                  sample_scale.data_ptr() if sample_scale is not None else None,
@@ -96,7 +140,8 @@ def _scale_residual_fwd(shortcut, z, gamma, sample_scale, emit_lowp):
 
 def _scale_residual_bwd(z, gamma, sample_scale, shortcut_dtype, dout, dout16):
     """-> (dshortcut, dz, dgamma, colsum of dz over (n, p) = the bias gradient of the Linear that produced z)"""
-    N, H, W, C = z.shape
+    N, H, W, ldc = z.shape
+    C = gamma.shape[0]                                 # (pitched z: ldc > C; dz gets the same pitch, zeros in its columns c >= C)
     if dout is None:                                   # only the bf16 copy was used downstream
         dout = torch.zeros((N, C, H, W), dtype=torch.float32, device=z.device)
     dout = dout.contiguous()
@@ -111,6 +156,17 @@ def _scale_residual_bwd(z, gamma, sample_scale, shortcut_dtype, dout, dout16):
     dgamma = torch.empty_like(gamma)
     dzc = torch.empty_like(gamma)
     L = _lib.lib()
+    if ldc != C:
+        ws, nb = _workspace(_tail_ws_bytes(N, ldc, H * W), z.device)
+        with _on(z.device):
+            _lib.check(L.slak_scale_residual_backward_ld(dout.data_ptr(), dout16.data_ptr() if dout16 is not None else None,
+                                                         dsum.data_ptr() if dsum is not None else None, z.data_ptr(), gamma.data_ptr(),
+                                                         sample_scale.data_ptr() if sample_scale is not None else None,
+                                                         dz.data_ptr(), dgamma.data_ptr(), dzc.data_ptr(), N, C, H * W,
+                                                         ws.data_ptr() if ws is not None else None, nb, _stream(z.device), ldc),
+                       "slak_scale_residual_backward_ld")
+        dsc = dsum if dsum is not None else dout
+        return (dsc if shortcut_dtype == torch.float32 else dsc.to(shortcut_dtype)), dz, dgamma, dzc
     ws, nb = _workspace(L.slak_block_tail_workspace_bytes(N, C, H * W), z.device)
     with _on(z.device):
         _lib.check(L.slak_scale_residual_backward(dout.data_ptr(), dout16.data_ptr() if dout16 is not None else None,
@@ -356,11 +412,21 @@ def tri_dwconv_sum(x, w_vertical, w_horizontal, w_small, bias=None):
 
 
 def ln_nchw_to_nhwc(x, weight, bias, eps=1e-6):
-    return _LnNchwToNhwc.apply(x, weight, bias, eps)
+    return _LnNchwToNhwc.apply(x, weight, bias, eps, None)
+
+
+def ln_nchw_to_nhwc_pitched(x, weight, bias, eps=1e-6, ldc=None):
+    """The same LayerNorm with rows of ``ldc`` (default nhwc_pitch(C)) elements: (N,H,W,ldc), exact zeros in the columns c >= C (any C <= 1024)."""
+    ldc = nhwc_pitch(x.shape[1]) if ldc is None else int(ldc)
+    if ldc is None:
+        raise _lib.SlakHipError("ln_nchw_to_nhwc_pitched: no NHWC pitch for C = %d (C <= 1024)" % x.shape[1])
+    return _LnNchwToNhwc.apply(x, weight, bias, eps, ldc)
 
 
 def scale_residual(shortcut, z, gamma, sample_scale=None, emit_lowp=False):
     """Returns `out` (fp32 NCHW), or (out, out_bf16) with emit_lowp."""
+    if z.dim() != 4 or z.shape[-1] != shortcut.shape[1]:
+        raise RuntimeError("z must be (N,H,W,C)")
     return _ScaleResidual.apply(shortcut, z, gamma, sample_scale, emit_lowp)
 
 
@@ -997,6 +1063,91 @@ def lowp_param_t(p):
     return e[2]
 
 
+# Zero-padded bf16 copies of the pointwise weights and biases of a PITCHED block (nhwc_pitch(C) != C: the width-1.3 models), in both orientations:
+# W1 [4C][C] -> [4 ldc][ldc], W2 [C][4C] -> [ldc][4 ldc], their transposes, b1 -> [4 ldc], b2 -> [ldc].  Kept like the copies above -- keyed by parameter
+# identity (+ padded shape and orientation), validated by the version counter, ALL stale ones refreshed in ONE slak_pad_cast_bf16_batch launch at the
+# first use after an optimizer step -- when cache_lowp_weights is on; otherwise a call makes its own copies (one launch for the six of a block).
+_pad_cache = {}               # (id(parameter), rows, cols, transposed) -> [weakref(parameter), version, bf16 copy]
+
+
+def _pad_cast_launch(jobs, device):
+    """jobs: (fp32 parameter, destination, transposed).  One launch."""
+    import ctypes
+    keep = []
+    for p, _, _ in jobs:
+        q = p.detach()
+        if q.dtype != torch.float32 or not q.is_contiguous():
+            q = q.float().contiguous()
+        keep.append(q)
+    n = len(jobs)
+    dims = [((1, q.shape[0]) if q.dim() == 1 else tuple(q.shape)) for q in keep]
+    ddims = [((1, d.shape[0]) if d.dim() == 1 else tuple(d.shape)) for _, d, _ in jobs]
+    arr_p, arr_i = ctypes.c_void_p * n, ctypes.c_int * n
+    with _on(device):
+        _lib.check(_lib.lib().slak_pad_cast_bf16_batch(arr_p(*[q.data_ptr() for q in keep]), arr_p(*[d.data_ptr() for _, d, _ in jobs]),
+                                                       arr_i(*[r for r, _ in dims]), arr_i(*[c for _, c in dims]),
+                                                       arr_i(*[r for r, _ in ddims]), arr_i(*[c for _, c in ddims]),
+                                                       arr_i(*[1 if tr else 0 for _, _, tr in jobs]), n, _stream(device)), "slak_pad_cast_bf16_batch")
+
+
+def refresh_padded(device=None):
+    """Refresh every stale padded copy (of `device`, default: all devices) -- one launch per device.  -> number of copies refreshed."""
+    by_dev, dead = {}, []
+    for key, e in _pad_cache.items():
+        p = e[0]()
+        if p is None:
+            dead.append(key)
+        elif e[1] != p._version and e[2].device == p.device and (device is None or p.device == device):
+            by_dev.setdefault(p.device, []).append((p, e))
+    for key in dead:
+        del _pad_cache[key]
+    for dev, items in by_dev.items():
+        _pad_cast_launch([(p, e[2], e[3]) for p, e in items], dev)
+        for p, e in items:
+            e[1] = p._version
+    return sum(len(v) for v in by_dev.values())
+
+
+def padded_cache_entries():
+    """(parameter, padded bf16 copy, transposed) of every live cache entry (tests)."""
+    return [(e[0](), e[2], e[3]) for e in _pad_cache.values() if e[0]() is not None]
+
+
+def padded_params(specs):
+    """specs: (parameter, rows, cols, transposed) per copy wanted -> the zero-padded bf16 copies ([rows][cols]; a 1-D parameter: rows == 1, result [cols])."""
+    dev = specs[0][0].device
+    outs, fresh, stale = [], [], False
+    for p, rows, cols, tr in specs:
+        shape = (cols,) if p.dim() == 1 else (rows, cols)
+        if not cache_lowp_weights:
+            c = torch.empty(shape, dtype=torch.bfloat16, device=p.device)
+            fresh.append((p, c, bool(tr)))
+            outs.append(c)
+            continue
+        key = (id(p), rows, cols, bool(tr))
+        e = _pad_cache.get(key)
+        if e is None or e[0]() is not p or e[2].device != p.device:
+            e = _pad_cache[key] = [_weakref.ref(p), None, torch.empty(shape, dtype=torch.bfloat16, device=p.device), bool(tr)]
+        stale = stale or e[1] != p._version
+        outs.append(e[2])
+    if fresh:
+        _pad_cast_launch(fresh, dev)
+    if stale:
+        refresh_padded(dev)
+    return outs
+
+
+def _pitched_operands(w1, b1, w2, b2, ldc):
+    """-> (W1p, b1p, W2p, b2p, W1p^T, W2p^T) for a block whose NHWC rows have pitch ldc."""
+    return padded_params([(w1, 4 * ldc, ldc, False), (b1, 1, 4 * ldc, False), (w2, ldc, 4 * ldc, False), (b2, 1, ldc, False),
+                          (w1, ldc, 4 * ldc, True), (w2, 4 * ldc, ldc, True)])
+
+
+def _cut_pitched_grads(C, dw1, db1, dw2):
+    """The padded GEMMs' weight / bias gradients cut back to the parameters' shapes (contiguous fp32; the pad rows and columns hold zeros)."""
+    return dw1[:4 * C, :C].contiguous(), db1[:4 * C].contiguous(), dw2[:C, :4 * C].contiguous()
+
+
 def w1_fragments(w1t):
     """W1^T [96][384] bf16 -> the fragment-major copy slak_linear_nt_gelu_bwd_dt reads ([pair][k-step][row tile][lane half][row][8 k]: 1 KB per
     load, every byte used); kept on the cached transpose it was made from until lowp_param_t refreshes that one."""
@@ -1108,9 +1259,11 @@ def linear_gemm_dgelu(dz2, w2t, y12):
     return dy1, db1
 
 
-def _mlp_fwd(t, w1, b1, w2, b2):
+def _mlp_fwd(t, w1, b1, w2, b2, cast=None):
+    """cast: parameter -> the bf16 operand the GEMMs read (default lowp_param; a pitched block hands its zero-padded copies)."""
     F = torch.nn.functional
-    w1b, w2b = lowp_param(w1), lowp_param(w2)
+    cast = lowp_param if cast is None else cast
+    w1b, w2b = cast(w1), cast(w2)
     L = _lib.lib()
     C, C4 = w1b.shape[1], w1b.shape[0]
     M = t.numel() // C
@@ -1120,22 +1273,22 @@ def _mlp_fwd(t, w1, b1, w2, b2):
         y1 = torch.empty(t.shape[:-1] + (C4,), dtype=torch.bfloat16, device=t.device)
         a = torch.empty_like(y1)
         z = torch.empty(t.shape[:-1] + (C,), dtype=torch.bfloat16, device=t.device)
-        bb1, bb2 = lowp_param(b1), lowp_param(b2)
+        bb1, bb2 = cast(b1), cast(b2)
         with _on(t.device):
             _lib.check(L.slak_linear_mlp_fwd(t.data_ptr(), w1b.data_ptr(), bb1.data_ptr(), w2b.data_ptr(), bb2.data_ptr(), y1.data_ptr(), a.data_ptr(),
                                              z.data_ptr(), M, C, C4, _stream(t.device)), "slak_linear_mlp_fwd")
         return z, (t, w1b, y1, a, w2b)
-    r = linear_nt(t, w1b, lowp_param(b1), gelu=True)            # pwconv1 + GELU in one streaming pass on the large maps
+    r = linear_nt(t, w1b, cast(b1), gelu=True)            # pwconv1 + GELU in one streaming pass on the large maps
     if r is None and b1 is not None:
-        r = linear_gemm_gelu(t, w1b, lowp_param(b1))            # stages 2-3: the GEMM with bias, rounding and GELU in its epilogue (y1 AND a in one launch)
+        r = linear_gemm_gelu(t, w1b, cast(b1))            # stages 2-3: the GEMM with bias, rounding and GELU in its epilogue (y1 AND a in one launch)
     if r is not None:
         y1, a = r
     else:
-        y1 = F.linear(t, w1b, lowp_param(b1))
+        y1 = F.linear(t, w1b, cast(b1))
         a = F.gelu(y1)
-    z = linear_nt(a, w2b, lowp_param(b2))
+    z = linear_nt(a, w2b, cast(b2))
     if z is None:
-        z = F.linear(a, w2b, lowp_param(b2))
+        z = F.linear(a, w2b, cast(b2))
     return z, (t, w1b, y1, a, w2b)
 
 
@@ -1257,6 +1410,22 @@ class _MlpScaleResidual(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, shortcut, t, w1, b1, w2, b2, gamma, sample_scale, emit_lowp):
+        C, ldc = shortcut.shape[1], t.shape[-1]
+        ctx.pitch = None
+        if ldc != C:                                                  # pitched t (ln_nchw_to_nhwc_pitched): the GEMMs read zero-padded weight copies
+            global pitched_block_hits
+            if w1.shape != (4 * C, C) or w2.shape != (C, 4 * C) or b1 is None or b2 is None or ldc < C or ldc % 8:
+                raise RuntimeError("mlp_scale_residual: t (..., %d) does not fit pointwise weights %s / %s" % (ldc, tuple(w1.shape), tuple(w2.shape)))
+            w1p, b1p, w2p, b2p, w1pt, w2pt = _pitched_operands(w1, b1, w2, b2, ldc)
+            tab = {id(w1): w1p, id(b1): b1p, id(w2): w2p, id(b2): b2p}
+            z, saved = _mlp_fwd(t, w1, b1, w2, b2, cast=lambda p: tab[id(p)])
+            z = z.contiguous()
+            out, out16 = _scale_residual_fwd(shortcut, z, gamma, sample_scale, emit_lowp)
+            ctx.save_for_backward(*saved, z, gamma, sample_scale, w1pt, w2pt)
+            ctx.shortcut_dtype = shortcut.dtype
+            ctx.pitch = (C, ldc)
+            pitched_block_hits += 1
+            return (out, out16) if emit_lowp else out
         z, saved = _mlp_fwd(t, w1, b1, w2, b2)
         if z.dtype != torch.bfloat16:
             z = z.to(torch.bfloat16)
@@ -1268,6 +1437,13 @@ class _MlpScaleResidual(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout, dout16=None):
+        if ctx.pitch is not None:
+            *saved, z, gamma, sample_scale, w1pt, w2pt = ctx.saved_tensors
+            dshortcut, dz, dgamma, dzc = _scale_residual_bwd(z, gamma, sample_scale, ctx.shortcut_dtype, dout, dout16)
+            dt, dy1, db1 = _mlp_bwd_data(saved, dz, (w1pt, w2pt))
+            dw1, dw2 = _mlp_bwd_weights(saved, dz, dy1)
+            dw1, db1, dw2 = _cut_pitched_grads(ctx.pitch[0], dw1, db1, dw2)
+            return dshortcut, dt, dw1, db1, dw2, dzc, dgamma, None, None
         *saved, z, gamma, sample_scale = ctx.saved_tensors
         dshortcut, dz, dgamma, dzc = _scale_residual_bwd(z, gamma, sample_scale, ctx.shortcut_dtype, dout, dout16)
         dt, dw1, db1, dw2, db2 = _mlp_bwd(saved, dz, db2=dzc)
@@ -1417,7 +1593,13 @@ class _BlockFn(torch.autograd.Function):
     def forward(ctx, x, x_lowp, wv, wh, ws, g1, b1, g2, b2, g3, b3, lnw, lnb, w1, bb1, w2, bb2, gamma, sample_scale, cfg):
         bns, eps, emit = cfg["bns"], cfg["eps"], cfg["emit_lowp"]
         ctx.runner = False
-        R = _runner()
+        C = x.shape[1]
+        ldc = nhwc_pitch(C)
+        if ldc is None:
+            raise _lib.SlakHipError("fused_block: no fused tail for C = %d (C <= 1024)" % C)
+        ctx.pitch = (C, ldc) if ldc != C else None
+        R = _runner() if ldc == C else None                           # the C++ runner issues the plain entry points only: a pitched block (odd C, or an even
+        # width under pad_even_widths) takes the Python sequence below
         if (R is not None and bns[0].momentum is not None and x.is_contiguous()
                 and all(bn.track_running_stats and bn.num_batches_tracked is not None for bn in bns)):
             w1b, w2b = lowp_param(w1), lowp_param(w2)
@@ -1444,13 +1626,23 @@ class _BlockFn(torch.autograd.Function):
         group = _bn3_group(bns[0])
         pre = _bn3_pre_rows(_stats_triple(st, x.device), x16.shape[1]) if st is not None else None
         s, bnstats, count, count_dev = _bn3_forward_impl(yv, yh, ys, [g1, g2, g3], [b1, b2, b3], bns, group, pre)
-        t, mean, rstd = _ln_fwd_impl(s, lnw, lnb, eps)
-        z, saved = _mlp_fwd(t, w1, bb1, w2, bb2)
+        t, mean, rstd = _ln_fwd_impl(s, lnw, lnb, eps, ldc)
+        if ctx.pitch is not None:
+            global pitched_block_hits
+            w1p, b1p, w2p, b2p, w1pt, w2pt = _pitched_operands(w1, bb1, w2, bb2, ldc)
+            tab = {id(w1): w1p, id(bb1): b1p, id(w2): w2p, id(bb2): b2p}
+            z, saved = _mlp_fwd(t, w1, bb1, w2, bb2, cast=lambda p: tab[id(p)])
+            pitched_block_hits += 1
+        else:
+            z, saved = _mlp_fwd(t, w1, bb1, w2, bb2)
         if z.dtype != torch.bfloat16:
             z = z.to(torch.bfloat16)
         z = z.contiguous()
         out, out16 = _scale_residual_fwd(x, z, gamma, sample_scale, emit)
-        wts = (lowp_param_t(w1), lowp_param_t(w2)) if cache_lowp_weights else (None, None)
+        if ctx.pitch is not None:
+            wts = (w1pt, w2pt)
+        else:
+            wts = (lowp_param_t(w1), lowp_param_t(w2)) if cache_lowp_weights else (None, None)
         ctx.save_for_backward(x16, wv, wh, ws, yv, yh, ys, g1, g2, g3, bnstats, s, lnw, mean, rstd, *saved, z, gamma, sample_scale, *wts)
         ctx.misc = (tri_dgrad, group, count, count_dev, x.dtype, x_lowp is not None)
         ctx.set_materialize_grads(False)
@@ -1480,6 +1672,8 @@ class _BlockFn(torch.autograd.Function):
         d1, d2, d3, dgam, dbet = _bn3_backward_impl(ds, yv, yh, ys, [g1, g2, g3], bnstats, group, count, count_dev, between=weights)
         need = ctx.needs_input_grad
         dx16, dwv, dwh, dws = _tri_backward_impl(x16, wv, wh, ws, d1, d2, d3, tri_dgrad, need[0] or need[1], need[2:5])
+        if ctx.pitch is not None:
+            wg["dw1"], db1, wg["dw2"] = _cut_pitched_grads(ctx.pitch[0], wg["dw1"], db1, wg["dw2"])
         dx = dxl = None
         if had_lowp:
             dx, dxl = dshortcut, dx16

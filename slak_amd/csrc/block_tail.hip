@@ -874,6 +874,39 @@ static int reduce_partials(const float* part, float* tmp, float* out0, float* ou
     return SLAK_OK;
 }
 
+// The same sums over partial rows of two halves of `half` columns each of which only the first `cl` are real (the register-tile kernels of a pitched
+// launch write rows of 2 * ldc): out0[j] = sum_t part[t][j], out1[j] = sum_t part[t][half + j] for j < cl.  Same order of additions as above.
+__global__ __launch_bounds__(1024) void block_tail_reduce1_ld(const float* __restrict__ part, float* __restrict__ out0, float* __restrict__ out1, int half, int cl,
+                                                              int ntiles) {
+    __shared__ float acc[32][33];
+    const int cx = threadIdx.x & 31, g = threadIdx.x >> 5;
+    const int j = blockIdx.x * 32 + cx, width = 2 * half;
+    const bool live = j < width && (j < half ? j : j - half) < cl;
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    if (live) {
+        const float* p = part + j;
+        int t = g;
+        for (; t + 96 < ntiles; t += 128) {
+            s0 += p[(size_t)t * width]; s1 += p[(size_t)(t + 32) * width]; s2 += p[(size_t)(t + 64) * width]; s3 += p[(size_t)(t + 96) * width];
+        }
+        for (; t < ntiles; t += 32) s0 += p[(size_t)t * width];
+    }
+    acc[g][cx] = (s0 + s1) + (s2 + s3);
+    __syncthreads();
+    if (g == 0 && live) {
+        float t = 0.f;
+#pragma unroll
+        for (int k = 0; k < 32; ++k) t += acc[k][cx];
+        if (j < half) out0[j] = t; else out1[j - half] = t;
+    }
+}
+static int reduce_partials_ld(const float* part, float* out0, float* out1, int half, int cl, int ntiles, hipStream_t st) {
+    hipLaunchKernelGGL(block_tail_reduce1_ld, dim3((unsigned)((2 * half + 31) / 32)), dim3(1024), 0, st, part, out0, out1, half, cl, ntiles);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_last_hip_error(e); return SLAK_ERR_LAUNCH; }
+    return SLAK_OK;
+}
+
 int tail_reduce_columns(const float* part, float* out, int ntiles, int width, hipStream_t st) { return reduce_partials(part, nullptr, out, out, width, ntiles, width, st); }
 int tail_reduce_split(const float* part, float* out0, float* out1, int split, int ntiles, int width, hipStream_t st) { return reduce_partials(part, nullptr, out0, out1, split, ntiles, width, st); }
 
@@ -957,6 +990,258 @@ const float* gelu_grad_table_device() {
     if (hipMemcpy(d, h.data(), h.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); return nullptr; }
     tab[dev] = (const float*)d;
     return tab[dev];
+}
+
+// ===== pitched NHWC side (slak_*_ld): any channel count C <= 1024, NHWC rows of pitch ldc >= C (ldc % 8 == 0) =====
+// The width-1.3 models have C = 124 / 249 / 499 / 998: rows of 2 C bytes are not 16-byte (249, 499: not even 4-byte) aligned, and no pointwise GEMM
+// kernel covers K = C.  The NCHW tensors keep their logical C; the NHWC intermediates get rows of ldc = 128 / 256 / 512 / 1024 elements whose
+// columns c >= C hold exact zeros, so that the GEMMs run the standard shapes on zero-padded weights and the logical columns carry the unpadded sums.
+// Same scheme as variant B above (persistent workgroups, wavefront <-> pixel, lane <-> channel pair on the NHWC side), with three rules:
+//   * statistics and the 1/C factors run over c < C only (a pad channel's (0 - mean)^2 is not zero);
+//   * a pad column that is WRITTEN (y, dz) is written as +0.0 -- the destination is uninitialised memory and NaN * 0 in the next GEMM would
+//     poison the logical columns;
+//   * a pad column that could be READ (g, z) is never used: where it rides along in a channel pair it is dropped with a select, not a multiply.
+__device__ __forceinline__ void load_nhwc_tile_ld(uint16_t* zs, const uint16_t* __restrict__ zn, int C, int ldc, int P, int p0, int TP, int tid) {
+    const int cp = (C + 1) / 2, pitch = 2 * cp + 2;                // (odd C: the last pair's upper half is pad column C < ldc -- staged, never read)
+    for (int idx = tid; idx < TP * cp; idx += BT_THREADS) {
+        const int q = idx / cp, k = idx - q * cp, p = p0 + q;
+        unsigned v = 0u;
+        if (p < P) v = ((const unsigned*)(zn + (size_t)p * ldc))[k];
+        ((unsigned*)(zs + q * pitch))[k] = v;
+    }
+}
+
+__global__ __launch_bounds__(BT_THREADS) void ln_nchw_to_nhwc_fwd_ld_kernel(const uint16_t* __restrict__ x, const float* __restrict__ w,
+                                                                          const float* __restrict__ b, uint16_t* __restrict__ y,
+                                                                          float* __restrict__ mean, float* __restrict__ rstd,
+                                                                          const TailDims d, int ldc, float eps) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int C = d.C, P = d.P, TP = d.TP, pitch = TP + 2, cpl = ldc / 2;
+    uint16_t* xs = (uint16_t*)smem;                                        // [C][TP+2]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int tile = blockIdx.x; tile < d.ntiles; tile += gridDim.x) {
+        const int n = tile / d.tiles_per_image, p0 = (tile - n * d.tiles_per_image) * TP;
+        load_nchw_tile(xs, x + (size_t)n * C * P, C, P, p0, TP, tid);
+        __syncthreads();
+        uint16_t* yn = y + ((size_t)n * P + p0) * ldc;
+        for (int q = wave; q < TP && p0 + q < P; q += BT_THREADS / 64) {
+            float s = 0.f;
+            for (int c = lane; c < C; c += 64) s += bf2f(xs[c * pitch + q]);
+            const float mu = bt_wave_sum(s) / (float)C;
+            float ss = 0.f;
+            for (int c = lane; c < C; c += 64) { const float v = bf2f(xs[c * pitch + q]) - mu; ss += v * v; }
+            const float r = 1.0f / sqrtf(bt_wave_sum(ss) / (float)C + eps);
+            if (lane == 0) { mean[(size_t)n * P + p0 + q] = mu; rstd[(size_t)n * P + p0 + q] = r; }
+            for (int k = lane; k < cpl; k += 64) {                         // the whole row of ldc columns: zeros behind column C
+                const int c0 = 2 * k, c1 = 2 * k + 1;
+                const float v0 = c0 < C ? (bf2f(xs[c0 * pitch + q]) - mu) * r * w[c0] + b[c0] : 0.f;
+                const float v1 = c1 < C ? (bf2f(xs[c1 * pitch + q]) - mu) * r * w[c1] + b[c1] : 0.f;
+                ((unsigned*)(yn + (size_t)q * ldc))[k] = bt_pack2(v0, v1);
+            }
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(BT_THREADS) void ln_nchw_to_nhwc_bwd_ld_kernel(const uint16_t* __restrict__ g, const uint16_t* __restrict__ x,
+                                                                          const float* __restrict__ w, const float* __restrict__ mean,
+                                                                          const float* __restrict__ rstd, uint16_t* __restrict__ dx,
+                                                                          float* __restrict__ part, const TailDims d, int ldc) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int C = d.C, P = d.P, TP = d.TP, xp = TP + 2, cp = (C + 1) / 2;
+    uint16_t* xs = (uint16_t*)smem;                                                  // [C][TP+2]
+    float* red = (float*)(smem + (((size_t)C * xp * 2 + 15) & ~(size_t)15));       // [4 waves][2][C] at the end
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    constexpr int KMAX = 8;                                                          // channel pairs per lane: C <= 1024
+    float aw[2 * KMAX], ab[2 * KMAX];
+#pragma unroll
+    for (int i = 0; i < 2 * KMAX; ++i) { aw[i] = 0.f; ab[i] = 0.f; }
+    for (int tile = blockIdx.x; tile < d.ntiles; tile += gridDim.x) {
+        const int n = tile / d.tiles_per_image, p0 = (tile - n * d.tiles_per_image) * TP;
+        load_nchw_tile(xs, x + (size_t)n * C * P, C, P, p0, TP, tid);
+        __syncthreads();
+        const uint16_t* gn = g + ((size_t)n * P + p0) * ldc;
+        for (int q = wave; q < TP && p0 + q < P; q += BT_THREADS / 64) {
+            const float mu = mean[(size_t)n * P + p0 + q], r = rstd[(size_t)n * P + p0 + q];
+            const unsigned* gq = (const unsigned*)(gn + (size_t)q * ldc);
+            float s1 = 0.f, s2 = 0.f;
+            for (int k = lane; k < cp; k += 64) {
+                const unsigned gv = gq[k];
+                const int c0 = 2 * k, c1 = 2 * k + 1;
+                const bool ok1 = c1 < C;
+                const float g0 = bf2f((uint16_t)(gv & 0xffff)) * w[c0];
+                const float g1 = ok1 ? bf2f((uint16_t)(gv >> 16)) * w[c1] : 0.f;
+                const float xh1 = ok1 ? (bf2f(xs[c1 * xp + q]) - mu) * r : 0.f;
+                s1 += g0 + g1;
+                s2 += g0 * ((bf2f(xs[c0 * xp + q]) - mu) * r) + g1 * xh1;
+            }
+            const float m1 = bt_wave_sum(s1) / (float)C, m2 = bt_wave_sum(s2) / (float)C;
+#pragma unroll
+            for (int kk = 0; kk < KMAX; ++kk) {
+                const int k = lane + 64 * kk;
+                if (k < cp) {
+                    const unsigned gv = gq[k];
+                    const int c0 = 2 * k, c1 = 2 * k + 1;
+                    const bool ok1 = c1 < C;
+                    const float gr0 = bf2f((uint16_t)(gv & 0xffff)), gr1 = ok1 ? bf2f((uint16_t)(gv >> 16)) : 0.f;
+                    const float xh0 = (bf2f(xs[c0 * xp + q]) - mu) * r, xh1 = ok1 ? (bf2f(xs[c1 * xp + q]) - mu) * r : 0.f;
+                    aw[2 * kk] += gr0 * xh0; aw[2 * kk + 1] += gr1 * xh1; ab[2 * kk] += gr0; ab[2 * kk + 1] += gr1;
+                    xs[c0 * xp + q] = bt_f2bf(r * (gr0 * w[c0] - m1 - xh0 * m2));
+                    if (ok1) xs[c1 * xp + q] = bt_f2bf(r * (gr1 * w[c1] - m1 - xh1 * m2));
+                }
+            }
+        }
+        __syncthreads();
+        store_nchw_tile(xs, dx + (size_t)n * C * P, C, P, p0, TP, tid);
+        __syncthreads();
+    }
+#pragma unroll
+    for (int kk = 0; kk < KMAX; ++kk) {
+        const int k = lane + 64 * kk;
+        if (k < cp) {
+            const int c0 = 2 * k, c1 = 2 * k + 1;
+            red[(wave * 2 + 0) * C + c0] = aw[2 * kk]; red[(wave * 2 + 1) * C + c0] = ab[2 * kk];
+            if (c1 < C) { red[(wave * 2 + 0) * C + c1] = aw[2 * kk + 1]; red[(wave * 2 + 1) * C + c1] = ab[2 * kk + 1]; }
+        }
+    }
+    __syncthreads();
+    float* pt = part + (size_t)blockIdx.x * 2 * C;
+    for (int i = tid; i < 2 * C; i += BT_THREADS) {
+        const int which = i / C, c = i - which * C;
+        pt[i] = ((red[(0 * 2 + which) * C + c] + red[(1 * 2 + which) * C + c]) + red[(2 * 2 + which) * C + c]) + red[(3 * 2 + which) * C + c];
+    }
+}
+
+template <typename Tsc>
+__global__ __launch_bounds__(BT_THREADS) void scale_residual_fwd_ld_kernel(const Tsc* __restrict__ sc, const uint16_t* __restrict__ z,
+                                                                         const float* __restrict__ gamma, const float* __restrict__ scale,
+                                                                         float* __restrict__ out, uint16_t* __restrict__ out16, const TailDims d, int ldc) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int C = d.C, P = d.P, TP = d.TP, zp = 2 * ((C + 1) / 2) + 2;
+    uint16_t* zs = (uint16_t*)smem;                                        // [TP][zp]
+    const int tid = threadIdx.x;
+    for (int tile = blockIdx.x; tile < d.ntiles; tile += gridDim.x) {
+        const int n = tile / d.tiles_per_image, p0 = (tile - n * d.tiles_per_image) * TP;
+        load_nhwc_tile_ld(zs, z + (size_t)n * P * ldc, C, ldc, P, p0, TP, tid);
+        __syncthreads();
+        const float sn = scale ? scale[n] : 1.0f;
+        const Tsc* scn = sc + (size_t)n * C * P;
+        float* on = out + (size_t)n * C * P;
+        if ((P & 3) == 0) {
+            const int cpr = TP / 4;
+            for (int idx = tid; idx < C * cpr; idx += BT_THREADS) {
+                const int c = idx / cpr, qq = (idx - c * cpr) * 4;
+                if (p0 + qq < P) {
+                    const float gm = gamma[c] * sn;
+                    const size_t off = (size_t)c * P + p0 + qq;
+                    float4 o;
+                    o.x = to_f32(scn[off + 0]) + gm * bf2f(zs[(qq + 0) * zp + c]);
+                    o.y = to_f32(scn[off + 1]) + gm * bf2f(zs[(qq + 1) * zp + c]);
+                    o.z = to_f32(scn[off + 2]) + gm * bf2f(zs[(qq + 2) * zp + c]);
+                    o.w = to_f32(scn[off + 3]) + gm * bf2f(zs[(qq + 3) * zp + c]);
+                    *(float4*)(on + off) = o;
+                    if (out16) *(uint2*)(out16 + (size_t)n * C * P + off) = uint2{bt_pack2(o.x, o.y), bt_pack2(o.z, o.w)};
+                }
+            }
+        } else {
+            for (int idx = tid; idx < C * TP; idx += BT_THREADS) {
+                const int c = idx / TP, qq = idx - c * TP;
+                if (p0 + qq < P) {
+                    const size_t off = (size_t)c * P + p0 + qq;
+                    const float ov = to_f32(scn[off]) + gamma[c] * sn * bf2f(zs[qq * zp + c]);
+                    on[off] = ov;
+                    if (out16) out16[(size_t)n * C * P + off] = bt_f2bf(ov);
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(BT_THREADS) void scale_residual_bwd_ld_kernel(const float* __restrict__ dout, const uint16_t* __restrict__ dout16, float* __restrict__ dsum,
+                                                                         const uint16_t* __restrict__ z,
+                                                                         const float* __restrict__ gamma, const float* __restrict__ scale,
+                                                                         uint16_t* __restrict__ dz, float* __restrict__ part, const TailDims d, int ldc) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int C = d.C, P = d.P, TP = d.TP, dp = TP + 1, cpl = ldc / 2;
+    float* ds = (float*)smem;                                                        // [C][TP+1] fp32
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    constexpr int KMAX = 8;                                                          // channel pairs per lane: ldc <= 1024
+    float ag[2 * KMAX], bg[2 * KMAX];
+#pragma unroll
+    for (int i = 0; i < 2 * KMAX; ++i) { ag[i] = 0.f; bg[i] = 0.f; }
+    for (int tile = blockIdx.x; tile < d.ntiles; tile += gridDim.x) {
+        const int n = tile / d.tiles_per_image, p0 = (tile - n * d.tiles_per_image) * TP;
+        const float* dn = dout + (size_t)n * C * P;
+        if ((P & 3) == 0) {
+            const int cpr = TP / 4;
+            for (int idx = tid; idx < C * cpr; idx += BT_THREADS) {
+                const int c = idx / cpr, qq = (idx - c * cpr) * 4;
+                float4 v = float4{0.f, 0.f, 0.f, 0.f};
+                if (p0 + qq < P) {
+                    const size_t off = (size_t)c * P + p0 + qq;
+                    v = *(const float4*)(dn + off);
+                    if (dout16) {
+                        const uint2 h = *(const uint2*)(dout16 + (size_t)n * C * P + off);
+                        v.x += bf2f((uint16_t)(h.x & 0xffff)); v.y += bf2f((uint16_t)(h.x >> 16));
+                        v.z += bf2f((uint16_t)(h.y & 0xffff)); v.w += bf2f((uint16_t)(h.y >> 16));
+                        *(float4*)(dsum + (size_t)n * C * P + off) = v;
+                    }
+                }
+                float* dst = ds + c * dp + qq;
+                dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w;
+            }
+        } else {
+            for (int idx = tid; idx < C * TP; idx += BT_THREADS) {
+                const int c = idx / TP, qq = idx - c * TP;
+                float v = 0.f;
+                if (p0 + qq < P) {
+                    const size_t off = (size_t)c * P + p0 + qq;
+                    v = dn[off];
+                    if (dout16) { v += bf2f(dout16[(size_t)n * C * P + off]); dsum[(size_t)n * C * P + off] = v; }
+                }
+                ds[c * dp + qq] = v;
+            }
+        }
+        __syncthreads();
+        const float sn = scale ? scale[n] : 1.0f;
+        const uint16_t* zn = z + ((size_t)n * P + p0) * ldc;
+        uint16_t* dzn = dz + ((size_t)n * P + p0) * ldc;
+        for (int q = wave; q < TP && p0 + q < P; q += BT_THREADS / 64) {
+            const unsigned* zq = (const unsigned*)(zn + (size_t)q * ldc);
+#pragma unroll
+            for (int kk = 0; kk < KMAX; ++kk) {
+                const int k = lane + 64 * kk;
+                if (k < cpl) {                                                       // the whole row of ldc columns: zeros behind column C
+                    const int c0 = 2 * k, c1 = 2 * k + 1;
+                    const bool ok0 = c0 < C, ok1 = c1 < C;
+                    const unsigned zv = ok0 ? zq[k] : 0u;
+                    const float d0 = ok0 ? ds[c0 * dp + q] : 0.f, d1 = ok1 ? ds[c1 * dp + q] : 0.f;
+                    const float zf0 = bf2f((uint16_t)(zv & 0xffff)), zf1 = ok1 ? bf2f((uint16_t)(zv >> 16)) : 0.f;
+                    ag[2 * kk] += sn * d0 * zf0; ag[2 * kk + 1] += sn * d1 * zf1;
+                    const float z0 = ok0 ? sn * gamma[c0] * d0 : 0.f, z1 = ok1 ? sn * gamma[c1] * d1 : 0.f;
+                    bg[2 * kk] += z0; bg[2 * kk + 1] += z1;
+                    ((unsigned*)(dzn + (size_t)q * ldc))[k] = bt_pack2(z0, z1);
+                }
+            }
+        }
+        __syncthreads();
+    }
+    float* red = ds;                                                                 // 2 x [4][C], the tile is dead now
+    float* red2 = ds + 4 * C;
+#pragma unroll
+    for (int kk = 0; kk < KMAX; ++kk) {
+        const int k = lane + 64 * kk;
+        const int c0 = 2 * k, c1 = 2 * k + 1;
+        if (c0 < C) { red[wave * C + c0] = ag[2 * kk]; red2[wave * C + c0] = bg[2 * kk]; }
+        if (c1 < C) { red[wave * C + c1] = ag[2 * kk + 1]; red2[wave * C + c1] = bg[2 * kk + 1]; }
+    }
+    __syncthreads();
+    float* pt = part + (size_t)blockIdx.x * 2 * C;               // [dgamma partial | column sums of dz]
+    for (int c = tid; c < C; c += BT_THREADS) {
+        pt[c] = ((red[c] + red[C + c]) + red[2 * C + c]) + red[3 * C + c];
+        pt[C + c] = ((red2[c] + red2[C + c]) + red2[2 * C + c]) + red2[3 * C + c];
+    }
 }
 
 }  // namespace slak
@@ -1227,6 +1512,110 @@ int slak_scale_residual_backward(const float* dout, const void* dout_bf16, float
     float* part = (float*)workspace;
     hipLaunchKernelGGL(scale_residual_bwd_kernel, dim3((unsigned)grid), dim3(BT_THREADS), lds, (hipStream_t)stream,
                        dout, (const uint16_t*)dout_bf16, dout_sum, (const uint16_t*)z, gamma, sample_scale, (uint16_t*)dz, part, d);
+    SLAK_LAUNCH_CHECK();
+    return reduce_partials(part, part + (size_t)grid * 2 * C, dgamma, dz_colsum, C, grid, 2 * C, (hipStream_t)stream);
+}
+
+// ---- pitched NHWC side: any C <= 1024, rows of ldc >= C elements (ldc % 8 == 0, <= 1024); ldc == C is the plain entry point, bit for bit
+static int tail_args_ok_ld(int N, int C, int P, int ldc) {
+    if (N <= 0 || C <= 0 || P <= 0) return SLAK_ERR_INVALID_ARG;
+    if (C > 1024 || ldc < C || (ldc & 7) || ldc > 1024) return SLAK_ERR_UNSUPPORTED;
+    if ((long long)N * ldc * P >= (1LL << 31)) return SLAK_ERR_UNSUPPORTED;
+    return SLAK_OK;
+}
+
+int slak_ln_nchw_to_nhwc_forward_ld(const void* x, const float* weight, const float* bias, void* y, float* mean, float* rstd,
+                                    int N, int C, int P, float eps, void* stream, int ldc) {
+    if (!x || !weight || !bias || !y || !mean || !rstd) return SLAK_ERR_INVALID_ARG;
+    int rc = tail_args_ok_ld(N, C, P, ldc); if (rc) return rc;
+    if (ldc == C) return slak_ln_nchw_to_nhwc_forward(x, weight, bias, y, mean, rstd, N, C, P, eps, stream);
+    if (tail_use_reg()) {                               // register-tile kernel on the instantiation whose channel count is the pitch
+        rc = launch_ln_nchw_to_nhwc_fwd_reg_ld(x, weight, bias, y, mean, rstd, N, C, ldc, P, eps, (hipStream_t)stream);
+        if (rc != SLAK_ERR_UNSUPPORTED) return rc;
+    }
+    const TailDims d = make_dims(N, C, P, 2);
+    const size_t lds = (size_t)C * (d.TP + 2) * 2 + 16;
+    if (set_lds((const void*)ln_nchw_to_nhwc_fwd_ld_kernel, lds)) return SLAK_ERR_LAUNCH;
+    hipLaunchKernelGGL(ln_nchw_to_nhwc_fwd_ld_kernel, dim3((unsigned)tail_grid(d, lds)), dim3(BT_THREADS), lds, (hipStream_t)stream,
+                       (const uint16_t*)x, weight, bias, (uint16_t*)y, mean, rstd, d, ldc, eps);
+    SLAK_LAUNCH_CHECK();
+    return SLAK_OK;
+}
+
+int slak_ln_nchw_to_nhwc_backward_ld(const void* g, const void* x, const float* weight, const float* mean, const float* rstd,
+                                     void* dx, float* dweight, float* dbias, int N, int C, int P,
+                                     void* workspace, size_t workspace_bytes, void* stream, int ldc) {
+    if (!g || !x || !weight || !mean || !rstd || !dx || !dweight || !dbias) return SLAK_ERR_INVALID_ARG;
+    int rc = tail_args_ok_ld(N, C, P, ldc); if (rc) return rc;
+    if (ldc == C) return slak_ln_nchw_to_nhwc_backward(g, x, weight, mean, rstd, dx, dweight, dbias, N, C, P, workspace, workspace_bytes, stream);
+    if (!workspace || workspace_bytes < slak_block_tail_workspace_bytes(N, ldc, P)) return SLAK_ERR_WORKSPACE;
+    if (tail_use_reg()) {
+        int rows = 0;
+        rc = launch_ln_nchw_to_nhwc_bwd_reg_ld(g, x, weight, mean, rstd, dx, (float*)workspace, &rows, N, C, ldc, P, (hipStream_t)stream);
+        if (rc == SLAK_OK) return reduce_partials_ld((const float*)workspace, dweight, dbias, ldc, C, rows, (hipStream_t)stream);
+        if (rc != SLAK_ERR_UNSUPPORTED) return rc;
+    }
+    const TailDims d = make_dims(N, C, P, 2);
+    const size_t lds = (((size_t)C * (d.TP + 2) * 2 + 15) & ~(size_t)15) + (size_t)4 * 2 * C * 4;
+    if (set_lds((const void*)ln_nchw_to_nhwc_bwd_ld_kernel, lds)) return SLAK_ERR_LAUNCH;
+    const int grid = tail_grid(d, lds);
+    float* part = (float*)workspace;
+    hipLaunchKernelGGL(ln_nchw_to_nhwc_bwd_ld_kernel, dim3((unsigned)grid), dim3(BT_THREADS), lds, (hipStream_t)stream,
+                       (const uint16_t*)g, (const uint16_t*)x, weight, mean, rstd, (uint16_t*)dx, part, d, ldc);
+    SLAK_LAUNCH_CHECK();
+    return reduce_partials(part, part + (size_t)grid * 2 * C, dweight, dbias, C, grid, 2 * C, (hipStream_t)stream);
+}
+
+int slak_scale_residual_forward_ld(const void* shortcut, int shortcut_dtype, const void* z, const float* gamma, const float* sample_scale,
+                                   float* out, void* out_bf16, int N, int C, int P, void* stream, int ldc) {
+    if (!shortcut || !z || !gamma || !out) return SLAK_ERR_INVALID_ARG;
+    int rc = tail_args_ok_ld(N, C, P, ldc); if (rc) return rc;
+    if (ldc == C) return slak_scale_residual_forward(shortcut, shortcut_dtype, z, gamma, sample_scale, out, out_bf16, N, C, P, stream);
+    if (shortcut_dtype != SLAK_F32 && shortcut_dtype != SLAK_BF16) return SLAK_ERR_UNSUPPORTED;
+    if (tail_use_reg()) {
+        rc = launch_scale_residual_fwd_reg_ld(shortcut, shortcut_dtype, z, gamma, sample_scale, out, out_bf16, N, C, ldc, P, (hipStream_t)stream);
+        if (rc != SLAK_ERR_UNSUPPORTED) return rc;
+    }
+    const int zp = 2 * ((C + 1) / 2) + 2;                           // the NHWC tile is [TP][zp]: same byte count as [C][TP+2] up to the padding
+    TailDims d = make_dims(N, C, P, 2);
+    while (d.TP > 16 && (size_t)d.TP * zp * 2 > 50 * 1024) { d.TP /= 2; d.tiles_per_image = (P + d.TP - 1) / d.TP; d.ntiles = N * d.tiles_per_image; }
+    const size_t lds = (size_t)d.TP * zp * 2 + 16;
+    const dim3 grid((unsigned)tail_grid(d, lds));
+    if (shortcut_dtype == SLAK_F32) {
+        if (set_lds((const void*)scale_residual_fwd_ld_kernel<float>, lds)) return SLAK_ERR_LAUNCH;
+        hipLaunchKernelGGL(scale_residual_fwd_ld_kernel<float>, grid, dim3(BT_THREADS), lds, (hipStream_t)stream,
+                           (const float*)shortcut, (const uint16_t*)z, gamma, sample_scale, out, (uint16_t*)out_bf16, d, ldc);
+    } else {
+        if (set_lds((const void*)scale_residual_fwd_ld_kernel<bf16_t>, lds)) return SLAK_ERR_LAUNCH;
+        hipLaunchKernelGGL(scale_residual_fwd_ld_kernel<bf16_t>, grid, dim3(BT_THREADS), lds, (hipStream_t)stream,
+                           (const bf16_t*)shortcut, (const uint16_t*)z, gamma, sample_scale, out, (uint16_t*)out_bf16, d, ldc);
+    }
+    SLAK_LAUNCH_CHECK();
+    return SLAK_OK;
+}
+
+int slak_scale_residual_backward_ld(const float* dout, const void* dout_bf16, float* dout_sum, const void* z, const float* gamma,
+                                    const float* sample_scale, void* dz, float* dgamma, float* dz_colsum, int N, int C, int P,
+                                    void* workspace, size_t workspace_bytes, void* stream, int ldc) {
+    if (!dout || !z || !gamma || !dz || !dgamma || !dz_colsum || (dout_bf16 && !dout_sum)) return SLAK_ERR_INVALID_ARG;
+    int rc = tail_args_ok_ld(N, C, P, ldc); if (rc) return rc;
+    if (ldc == C) return slak_scale_residual_backward(dout, dout_bf16, dout_sum, z, gamma, sample_scale, dz, dgamma, dz_colsum, N, C, P,
+                                                      workspace, workspace_bytes, stream);
+    if (!workspace || workspace_bytes < slak_block_tail_workspace_bytes(N, ldc, P)) return SLAK_ERR_WORKSPACE;
+    if (tail_use_reg()) {
+        int rows = 0;
+        rc = launch_scale_residual_bwd_reg_ld(dout, dout_bf16, dout_sum, z, gamma, sample_scale, dz, (float*)workspace, &rows, N, C, ldc, P, (hipStream_t)stream);
+        if (rc == SLAK_OK) return reduce_partials_ld((const float*)workspace, dgamma, dz_colsum, ldc, C, rows, (hipStream_t)stream);
+        if (rc != SLAK_ERR_UNSUPPORTED) return rc;
+    }
+    const TailDims d = make_dims(N, C, P, 4);
+    size_t lds = (size_t)C * (d.TP + 1) * 4 + 16;
+    if (lds < (size_t)8 * C * 4 + 16) lds = (size_t)8 * C * 4 + 16;               // the per-wave partial sums reuse the tile: 2 x [4][C]
+    if (set_lds((const void*)scale_residual_bwd_ld_kernel, lds)) return SLAK_ERR_LAUNCH;
+    const int grid = tail_grid(d, lds);
+    float* part = (float*)workspace;
+    hipLaunchKernelGGL(scale_residual_bwd_ld_kernel, dim3((unsigned)grid), dim3(BT_THREADS), lds, (hipStream_t)stream,
+                       dout, (const uint16_t*)dout_bf16, dout_sum, (const uint16_t*)z, gamma, sample_scale, (uint16_t*)dz, part, d, ldc);
     SLAK_LAUNCH_CHECK();
     return reduce_partials(part, part + (size_t)grid * 2 * C, dgamma, dz_colsum, C, grid, 2 * C, (hipStream_t)stream);
 }

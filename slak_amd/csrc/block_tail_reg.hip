@@ -169,15 +169,28 @@ __device__ __forceinline__ float rt_f4(const float4& v, int k) { return k == 0 ?
 
 // y[n,p,:] = LN_C(x[n,:,p]) * w + b   (x bf16 or fp32 NCHW, y bf16 NHWC or patch matrix, statistics fp32, two-pass variance); saves mean,
 // rstd.  One tile per wave.  Wimg: image width (PATCH mode only).
-template <int CL, int G, bool XF32 = false, bool PATCH = false>
+// LD (the pitched entry points, slak_*_ld): the NCHW tensors have Cl <= C channel rows, the NHWC rows keep their C = CL * G columns (the pitch).
+// A lane's channel rows c >= Cl get the out-of-range lane offset, so they read as zeros and their stores are dropped by the range check
+// (never fetched from the next image; the descriptors also end behind row Cl - 1); what a zero row would still add to a sum -- (0 - mean)^2, a pad column of g or z that holds anything --
+// is dropped with a select per channel, and the per-channel parameters are staged as zeros behind Cl (pad columns of y and dz: +0).
+// (the channel row travels in the SCALAR offset of the buffer operations, which the range check need not cover: a row c >= Cl is turned away through the
+// lane offset, exactly like a lane past the end of the image)
+// RT_LD_PAD: at most this many pad columns (ldc - Cl; 4 / 7 / 13 at width 1.3), so only a lane's LAST RT_LD_PAD channels can be missing and only
+// they pay the select -- one per channel ROW in flight costs a register each, and 64 of them spill the backward kernels.
+constexpr int RT_LD_PAD = 16;
+#define RT_DEAD(c) (LD && (int)(c) >= CL - RT_LD_PAD && (int)(c) >= nlive)
+#define RT_VO(vo, c) ((LD && (int)(c) >= CL - RT_LD_PAD) ? ((int)(c) < nlive ? (vo) : RT_OOB) : (vo))
+template <int CL, int G, bool XF32 = false, bool PATCH = false, bool LD = false>
 __global__ __launch_bounds__(256, 2) void ln_nchw_to_nhwc_fwd_reg_kernel(const void* __restrict__ xin, const float* __restrict__ w,
                                                                         const float* __restrict__ b, uint16_t* __restrict__ y,
                                                                         float* __restrict__ mean, float* __restrict__ rstd,
-                                                                        int N, int P, float eps, int tiles_per_image, int ntiles, int Wimg) {
+                                                                        int N, int P, float eps, int tiles_per_image, int ntiles, int Wimg, int Cl) {
+    static_assert(!(LD && PATCH), "the patch matrix has no pitched form");
     using XR = RtX<XF32>;
     const char* const x = (const char*)xin;
     using GE = RtGeom<CL, G>;
     constexpr int C = GE::C, PW = GE::PW, PITCH = GE::PITCH;
+    const int Cq = LD ? Cl : C;                                                             // channel rows of the NCHW tensors
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     float* const Lw = (float*)(smem + 4 * GE::LDS_WAVE);
@@ -189,21 +202,27 @@ __global__ __launch_bounds__(256, 2) void ln_nchw_to_nhwc_fwd_reg_kernel(const v
     const int pp = lane / G, g = lane & (G - 1);
     const int rows = has_tile ? min(PW, P - p0) : 0;
     const unsigned rb = (unsigned)P * XR::EB;                                               // bytes per channel row
-    const rt_rsrc rx = rt_buf(x + ((size_t)n * C * P + p0) * XR::EB, (unsigned)(C * P - p0) * XR::EB);
+    const rt_rsrc rx = rt_buf(x + ((size_t)n * Cq * P + p0) * XR::EB, (unsigned)(Cq * P - p0) * XR::EB);
     const unsigned vo = 2 * pp < rows ? (unsigned)(g * CL) * rb + (unsigned)pp * 2u * XR::EB : RT_OOB;
+    const int nlive = Cl - g * CL;                                                          // LD: the lane's channels c < nlive exist
     typename XR::reg v[CL];                                                                 // (pixel p, pixel p+1) of channel c
 #pragma unroll
-    for (int c = 0; c < CL; ++c) v[c] = XR::load(rx, vo, (unsigned)c * rb);
-    for (int i = threadIdx.x; i < C; i += 256) { Lw[i] = w[i]; Lb[i] = b[i]; }              // behind the tile's loads: one memory latency, not two
+    for (int c = 0; c < CL; ++c) v[c] = XR::load(rx, RT_VO(vo, c), (unsigned)c * rb);
+    if constexpr (LD) { for (int i = threadIdx.x; i < C; i += 256) { Lw[i] = i < Cl ? w[i] : 0.f; Lb[i] = i < Cl ? b[i] : 0.f; } }
+    else { for (int i = threadIdx.x; i < C; i += 256) { Lw[i] = w[i]; Lb[i] = b[i]; } }     // behind the tile's loads: one memory latency, not two
     __syncthreads();
     float s0 = 0.f, s1 = 0.f;
 #pragma unroll
     for (int c = 0; c < CL; ++c) { s0 += XR::p0(v[c]); s1 += XR::p1(v[c]); }
-    const float mu0 = rt_group_sum<G>(s0) / (float)C, mu1 = rt_group_sum<G>(s1) / (float)C;
+    const float mu0 = rt_group_sum<G>(s0) / (float)Cq, mu1 = rt_group_sum<G>(s1) / (float)Cq;
     float q0 = 0.f, q1 = 0.f;
 #pragma unroll
-    for (int c = 0; c < CL; ++c) { const float a = XR::p0(v[c]) - mu0, d = XR::p1(v[c]) - mu1; q0 += a * a; q1 += d * d; }
-    const float r0 = 1.0f / sqrtf(rt_group_sum<G>(q0) / (float)C + eps), r1 = 1.0f / sqrtf(rt_group_sum<G>(q1) / (float)C + eps);
+    for (int c = 0; c < CL; ++c) {
+        float a = XR::p0(v[c]) - mu0, d = XR::p1(v[c]) - mu1;
+        if (RT_DEAD(c)) { a = 0.f; d = 0.f; }
+        q0 += a * a; q1 += d * d;
+    }
+    const float r0 = 1.0f / sqrtf(rt_group_sum<G>(q0) / (float)Cq + eps), r1 = 1.0f / sqrtf(rt_group_sum<G>(q1) / (float)Cq + eps);
     {
         const unsigned so = (g == 0 && 2 * pp < rows) ? (unsigned)pp * 8u : RT_OOB;
         __builtin_amdgcn_raw_buffer_store_b64(rt_u32x2{__float_as_uint(mu0), __float_as_uint(mu1)}, rt_buf(mean + (size_t)n * P + p0, (unsigned)(P - p0) * 4u), so, 0, 0);
@@ -233,15 +252,17 @@ __global__ __launch_bounds__(256, 2) void ln_nchw_to_nhwc_fwd_reg_kernel(const v
 
 // dx[n,:,p] = rstd * (g*w - mean_C(g*w) - xhat * mean_C(g*w*xhat)) (NCHW, bf16 or fp32 like x) from g (bf16 NHWC or patch matrix), x;
 // part[workgroup][0..C) = sum_p g * xhat, [C..2C) = sum_p g over its tiles.  Persistent waves (accumulators live in registers).
-template <int CL, int G, bool XF32 = false, bool PATCH = false>
+template <int CL, int G, bool XF32 = false, bool PATCH = false, bool LD = false>
 __global__ __launch_bounds__(256, 2) void ln_nchw_to_nhwc_bwd_reg_kernel(const uint16_t* __restrict__ gy, const void* __restrict__ xin,
                                                                         const float* __restrict__ w, const float* __restrict__ mean,
                                                                         const float* __restrict__ rstd, void* __restrict__ dxout,
-                                                                        float* __restrict__ part, int N, int P, int tiles_per_image, int ntiles, int Wimg) {
+                                                                        float* __restrict__ part, int N, int P, int tiles_per_image, int ntiles, int Wimg, int Cl) {
+    static_assert(!(LD && PATCH), "the patch matrix has no pitched form");
     using XR = RtX<XF32>;
     const char* const x = (const char*)xin; char* const dx = (char*)dxout;
     using GE = RtGeom<CL, G>;
     constexpr int C = GE::C, PW = GE::PW, PITCH = GE::PITCH;
+    const int Cq = LD ? Cl : C;                                                // channel rows of the NCHW tensors (LD: see the forward kernel)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     float* const Lw = (float*)(smem + 4 * GE::LDS_WAVE);
@@ -260,17 +281,18 @@ __global__ __launch_bounds__(256, 2) void ln_nchw_to_nhwc_bwd_reg_kernel(const u
         const int rows = min(PW, P - p0);
         if constexpr (PATCH) { rt_dma_plan_patch(plan, lane, p0, Wimg, rows); rt_tile_dma<C, PW>(plan, gy + (size_t)n * P * C, (unsigned)P * C * 2u, lds_T); }
         else rt_tile_dma<C, PW>(plan, gy + ((size_t)n * P + p0) * C, (unsigned)rows * C * 2u, lds_T);
-        const rt_rsrc rx = rt_buf(x + ((size_t)n * C * P + p0) * XR::EB, (unsigned)(C * P - p0) * XR::EB);
+        const rt_rsrc rx = rt_buf(x + ((size_t)n * Cq * P + p0) * XR::EB, (unsigned)(Cq * P - p0) * XR::EB);
         const bool valid = 2 * pp < rows;
         const unsigned vo = valid ? (unsigned)(g * CL) * rb + (unsigned)pp * 2u * XR::EB : RT_OOB;
+        const int nlive = Cl - g * CL;                                          // LD: the lane's channels c < nlive exist; the others' g columns are dropped
         typename XR::reg xv[CL];
 #pragma unroll
-        for (int c = 0; c < CL; ++c) xv[c] = XR::load(rx, vo, (unsigned)c * rb);
+        for (int c = 0; c < CL; ++c) xv[c] = XR::load(rx, RT_VO(vo, c), (unsigned)c * rb);
         const unsigned so = valid ? (unsigned)pp * 8u : RT_OOB;
         const rt_u32x2 mu2 = __builtin_amdgcn_raw_buffer_load_b64(rt_buf(mean + (size_t)n * P + p0, (unsigned)(P - p0) * 4u), so, 0, 0);
         const rt_u32x2 r2 = __builtin_amdgcn_raw_buffer_load_b64(rt_buf(rstd + (size_t)n * P + p0, (unsigned)(P - p0) * 4u), so, 0, 0);
         const float mu0 = __uint_as_float(mu2[0]), mu1 = __uint_as_float(mu2[1]), r0 = __uint_as_float(r2[0]), r1 = __uint_as_float(r2[1]);
-        if (!staged) { for (int i = threadIdx.x; i < C; i += 256) Lw[i] = w[i]; __syncthreads(); staged = true; }
+        if (!staged) { for (int i = threadIdx.x; i < C; i += 256) Lw[i] = (!LD || i < Cl) ? w[i] : 0.f; __syncthreads(); staged = true; }
         rt_dma_wait();
         // g is read from the LDS tile in both passes (rows past the image were written as zeros: g = 0 there); x stays packed in registers
         const unsigned char* const ra = T + (2 * pp) * PITCH + g * (CL * 2);
@@ -284,19 +306,20 @@ __global__ __launch_bounds__(256, 2) void ln_nchw_to_nhwc_bwd_reg_kernel(const u
 #pragma unroll
                 for (int k4 = 0; k4 < 4; ++k4) {
                     const int k = 4 * h + k4, c = 8 * j4 + k;
-                    const float gw0 = RT_CH(ta, k) * rt_f4(w4, k4), gw1 = RT_CH(tb, k) * rt_f4(w4, k4);
+                    float gw0 = RT_CH(ta, k) * rt_f4(w4, k4), gw1 = RT_CH(tb, k) * rt_f4(w4, k4);
+                    if (RT_DEAD(c)) { gw0 = 0.f; gw1 = 0.f; }
                     s10 += gw0; s11 += gw1;
                     s20 += gw0 * ((XR::p0(xv[c]) - mu0) * r0); s21 += gw1 * ((XR::p1(xv[c]) - mu1) * r1);
                 }
             }
             __builtin_amdgcn_sched_barrier(0);                                  // one octet's LDS reads and unpacked values live at a time
         }
-        const float m10 = rt_group_sum<G>(s10) / (float)C, m11 = rt_group_sum<G>(s11) / (float)C;
-        const float m20 = rt_group_sum<G>(s20) / (float)C, m21 = rt_group_sum<G>(s21) / (float)C;
+        const float m10 = rt_group_sum<G>(s10) / (float)Cq, m11 = rt_group_sum<G>(s11) / (float)Cq;
+        const float m20 = rt_group_sum<G>(s20) / (float)Cq, m21 = rt_group_sum<G>(s21) / (float)Cq;
         // second pass from the PACKED registers again: without this the compiler keeps the unpacked fp32 values of the first pass alive
 #pragma unroll
         for (int c = 0; c < CL; ++c) XR::opaque(xv[c]);
-        const rt_rsrc rdx = rt_buf(dx + ((size_t)n * C * P + p0) * XR::EB, (unsigned)(C * P - p0) * XR::EB);
+        const rt_rsrc rdx = rt_buf(dx + ((size_t)n * Cq * P + p0) * XR::EB, (unsigned)(Cq * P - p0) * XR::EB);
 #pragma unroll
         for (int j4 = 0; j4 < CL / 8; ++j4) {
             const rt_u32x4 ta = *(const rt_u32x4*)(ra + j4 * 16), tb = *(const rt_u32x4*)(ra + PITCH + j4 * 16);
@@ -308,9 +331,10 @@ __global__ __launch_bounds__(256, 2) void ln_nchw_to_nhwc_bwd_reg_kernel(const u
                 for (int k4 = 0; k4 < 4; ++k4) {
                     const int k = 4 * h + k4, c = 8 * j4 + k;
                     const float wc = rt_f4(w4, k4);
-                    const float g0 = RT_CH(ta, k), g1 = RT_CH(tb, k);
+                    float g0 = RT_CH(ta, k), g1 = RT_CH(tb, k);
+                    if (RT_DEAD(c)) { g0 = 0.f; g1 = 0.f; }
                     const float xh0 = (XR::p0(xv[c]) - mu0) * r0, xh1 = (XR::p1(xv[c]) - mu1) * r1;
-                    XR::store(rdx, vo, (unsigned)c * rb, r0 * (g0 * wc - m10 - xh0 * m20), r1 * (g1 * wc - m11 - xh1 * m21));
+                    XR::store(rdx, RT_VO(vo, c), (unsigned)c * rb, r0 * (g0 * wc - m10 - xh0 * m20), r1 * (g1 * wc - m11 - xh1 * m21));
                     tw[k4] = g0 * xh0 + g1 * xh1; ts[k4] = g0 + g1;
                 }
                 accw[2 * j4 + h] += rt_fold4(tw[0], tw[1], tw[2], tw[3]);
@@ -320,18 +344,19 @@ __global__ __launch_bounds__(256, 2) void ln_nchw_to_nhwc_bwd_reg_kernel(const u
         }
         rt_lds_fence();                                                        // tile consumed: the next iteration's DMA may overwrite it
     }
-    if (!staged) { for (int i = threadIdx.x; i < C; i += 256) Lw[i] = w[i]; __syncthreads(); }       // a wave without tiles still stages its share
+    if (!staged) { for (int i = threadIdx.x; i < C; i += 256) Lw[i] = (!LD || i < Cl) ? w[i] : 0.f; __syncthreads(); }       // a wave without tiles still stages its share
     rt_write_partials<CL, G>(accw, accb, part + (size_t)blockIdx.x * 2 * C, (float*)smem, wave, lane, [](float a, int) { return a; });
 }
 
 // out[n,c,p] (fp32 NCHW) = shortcut[n,c,p] + scale[n] * gamma[c] * z[n,p,c] (bf16 NHWC); optional bf16 copy of out.  One tile per wave.
-template <int CL, int G, typename Tsc>
+template <int CL, int G, typename Tsc, bool LD = false>
 __global__ __launch_bounds__(256, 2) void scale_residual_fwd_reg_kernel(const Tsc* __restrict__ sc, const uint16_t* __restrict__ z,
                                                                        const float* __restrict__ gamma, const float* __restrict__ scale,
                                                                        float* __restrict__ out, uint16_t* __restrict__ out16,
-                                                                       int N, int P, int tiles_per_image, int ntiles) {
+                                                                       int N, int P, int tiles_per_image, int ntiles, int Cl) {
     using GE = RtGeom<CL, G>;
     constexpr int C = GE::C, PW = GE::PW, PITCH = GE::PITCH;
+    const int Cq = LD ? Cl : C;                  // channel rows of the NCHW tensors (LD: a pad column of z only reaches stores that the range check drops)
     constexpr bool SC32 = sizeof(Tsc) == 4;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -352,16 +377,17 @@ __global__ __launch_bounds__(256, 2) void scale_residual_fwd_reg_kernel(const Ts
     const bool valid = 2 * pp < rows;
     const unsigned e0 = (unsigned)(g * CL) * P1 + 2u * (unsigned)pp;                     // element offset of the lane's first pixel
     const unsigned vo4 = valid ? e0 * 4u : RT_OOB, vo2 = valid ? e0 * 2u : RT_OOB;
-    const rt_rsrc rsc = rt_buf(sc + (size_t)n * C * P + p0, (unsigned)(C * P - p0) * (unsigned)sizeof(Tsc));
-    const rt_rsrc ro = rt_buf(out + (size_t)n * C * P + p0, (unsigned)(C * P - p0) * 4u);
-    const rt_rsrc ro16 = rt_buf(out16 ? out16 + (size_t)n * C * P + p0 : nullptr, out16 ? (unsigned)(C * P - p0) * 2u : 0u);
+    const rt_rsrc rsc = rt_buf(sc + (size_t)n * Cq * P + p0, (unsigned)(Cq * P - p0) * (unsigned)sizeof(Tsc));
+    const rt_rsrc ro = rt_buf(out + (size_t)n * Cq * P + p0, (unsigned)(Cq * P - p0) * 4u);
+    const rt_rsrc ro16 = rt_buf(out16 ? out16 + (size_t)n * Cq * P + p0 : nullptr, out16 ? (unsigned)(Cq * P - p0) * 2u : 0u);
+    const int nlive = Cl - g * CL;               // LD: the lane's channels c < nlive exist
     float sx[CL], sy[CL];                        // every channel row of the lane in flight at once (one memory latency for the whole tile)
 #pragma unroll
     for (int c = 0; c < CL; ++c) {
-        if constexpr (SC32) { const rt_u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rsc, vo4, (unsigned)c * P1 * 4u, 0); sx[c] = __uint_as_float(v[0]); sy[c] = __uint_as_float(v[1]); }
-        else { const unsigned v = __builtin_amdgcn_raw_buffer_load_b32(rsc, vo2, (unsigned)c * P1 * 2u, 0); sx[c] = rt_lo(v); sy[c] = rt_hi(v); }
+        if constexpr (SC32) { const rt_u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rsc, RT_VO(vo4, c), (unsigned)c * P1 * 4u, 0); sx[c] = __uint_as_float(v[0]); sy[c] = __uint_as_float(v[1]); }
+        else { const unsigned v = __builtin_amdgcn_raw_buffer_load_b32(rsc, RT_VO(vo2, c), (unsigned)c * P1 * 2u, 0); sx[c] = rt_lo(v); sy[c] = rt_hi(v); }
     }
-    for (int i = threadIdx.x; i < C; i += 256) Lg[i] = gamma[i];
+    for (int i = threadIdx.x; i < C; i += 256) Lg[i] = (!LD || i < Cl) ? gamma[i] : 0.f;
     __syncthreads();
     rt_dma_wait();
 #pragma unroll
@@ -376,8 +402,8 @@ __global__ __launch_bounds__(256, 2) void scale_residual_fwd_reg_kernel(const Ts
                 const int k = 4 * h + k4, c = j4 * 8 + k;
                 const float gm = rt_f4(g4, k4) * sn;
                 const float ox = sx[c] + gm * RT_CH(ta, k), oy = sy[c] + gm * RT_CH(tb, k);
-                __builtin_amdgcn_raw_buffer_store_b64(rt_u32x2{__float_as_uint(ox), __float_as_uint(oy)}, ro, vo4, (unsigned)c * P1 * 4u, 0);
-                if (out16) __builtin_amdgcn_raw_buffer_store_b32(rt_pack2(ox, oy), ro16, vo2, (unsigned)c * P1 * 2u, 0);
+                __builtin_amdgcn_raw_buffer_store_b64(rt_u32x2{__float_as_uint(ox), __float_as_uint(oy)}, ro, RT_VO(vo4, c), (unsigned)c * P1 * 4u, 0);
+                if (out16) __builtin_amdgcn_raw_buffer_store_b32(rt_pack2(ox, oy), ro16, RT_VO(vo2, c), (unsigned)c * P1 * 2u, 0);
             }
         }
     }
@@ -421,14 +447,15 @@ __global__ __launch_bounds__(256) void scale_residual_fwd_chan_kernel(const floa
 
 // dz[n,p,c] (bf16 NHWC) = scale[n] * gamma[c] * d[n,c,p], d = dout (fp32 NCHW) [+ dout16 (bf16 NCHW), the sum written to dsum];
 // part[wave][0..C) = sum scale * d * z, [C..2C) = gamma * sum scale * d.  Persistent waves; z and dz share the wave's LDS tile.
-template <int CL, int G>
+template <int CL, int G, bool LD = false>
 __global__ __launch_bounds__(256, 2) void scale_residual_bwd_reg_kernel(const float* __restrict__ dout, const uint16_t* __restrict__ dout16,
                                                                        float* __restrict__ dsum, const uint16_t* __restrict__ z,
                                                                        const float* __restrict__ gamma, const float* __restrict__ scale,
                                                                        uint16_t* __restrict__ dz, float* __restrict__ part,
-                                                                       int N, int P, int tiles_per_image, int ntiles) {
+                                                                       int N, int P, int tiles_per_image, int ntiles, int Cl) {
     using GE = RtGeom<CL, G>;
     constexpr int C = GE::C, PW = GE::PW, PITCH = GE::PITCH;
+    const int Cq = LD ? Cl : C;                                                // channel rows of the NCHW tensors (LD: see the LayerNorm forward kernel)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     float* const Lg = (float*)(smem + 4 * GE::LDS_WAVE);
@@ -450,16 +477,17 @@ __global__ __launch_bounds__(256, 2) void scale_residual_bwd_reg_kernel(const fl
         const bool valid = 2 * pp < rows;
         const unsigned e0 = (unsigned)(g * CL) * P1 + 2u * (unsigned)pp;
         const unsigned vo4 = valid ? e0 * 4u : RT_OOB, vo2 = valid ? e0 * 2u : RT_OOB;
-        const rt_rsrc rd = rt_buf(dout + (size_t)n * C * P + p0, (unsigned)(C * P - p0) * 4u);
-        const rt_rsrc rd16 = rt_buf(dout16 ? dout16 + (size_t)n * C * P + p0 : nullptr, dout16 ? (unsigned)(C * P - p0) * 2u : 0u);
-        const rt_rsrc rds = rt_buf(dout16 ? dsum + (size_t)n * C * P + p0 : nullptr, dout16 ? (unsigned)(C * P - p0) * 4u : 0u);
+        const rt_rsrc rd = rt_buf(dout + (size_t)n * Cq * P + p0, (unsigned)(Cq * P - p0) * 4u);
+        const rt_rsrc rd16 = rt_buf(dout16 ? dout16 + (size_t)n * Cq * P + p0 : nullptr, dout16 ? (unsigned)(Cq * P - p0) * 2u : 0u);
+        const rt_rsrc rds = rt_buf(dout16 ? dsum + (size_t)n * Cq * P + p0 : nullptr, dout16 ? (unsigned)(Cq * P - p0) * 4u : 0u);
+        const int nlive = Cl - g * CL;                                          // LD: the lane's channels c < nlive exist; the others' z columns are dropped
         rt_u32x2 dv[CL]; unsigned dh[CL];        // every channel row of the lane in flight at once
 #pragma unroll
         for (int c = 0; c < CL; ++c) {
-            dv[c] = __builtin_amdgcn_raw_buffer_load_b64(rd, vo4, (unsigned)c * P1 * 4u, 0);                       // lanes past the image: zeros
-            dh[c] = dout16 ? __builtin_amdgcn_raw_buffer_load_b32(rd16, vo2, (unsigned)c * P1 * 2u, 0) : 0u;
+            dv[c] = __builtin_amdgcn_raw_buffer_load_b64(rd, RT_VO(vo4, c), (unsigned)c * P1 * 4u, 0);             // lanes past the image: zeros
+            dh[c] = dout16 ? __builtin_amdgcn_raw_buffer_load_b32(rd16, RT_VO(vo2, c), (unsigned)c * P1 * 2u, 0) : 0u;
         }
-        if (!staged) { for (int i = threadIdx.x; i < C; i += 256) Lg[i] = gamma[i]; __syncthreads(); staged = true; }
+        if (!staged) { for (int i = threadIdx.x; i < C; i += 256) Lg[i] = (!LD || i < Cl) ? gamma[i] : 0.f; __syncthreads(); staged = true; }
         rt_dma_wait();
 #pragma unroll
         for (int j4 = 0; j4 < CL / 8; ++j4) {
@@ -473,10 +501,11 @@ __global__ __launch_bounds__(256, 2) void scale_residual_bwd_reg_kernel(const fl
                 float vx = __uint_as_float(dv[c][0]), vy = __uint_as_float(dv[c][1]);
                 if (dout16) {
                     vx += rt_lo(dh[c]); vy += rt_hi(dh[c]);
-                    __builtin_amdgcn_raw_buffer_store_b64(rt_u32x2{__float_as_uint(vx), __float_as_uint(vy)}, rds, vo4, c * P1 * 4u, 0);
+                    __builtin_amdgcn_raw_buffer_store_b64(rt_u32x2{__float_as_uint(vx), __float_as_uint(vy)}, rds, RT_VO(vo4, c), c * P1 * 4u, 0);
                 }
                 d0[k] = vx * sn; d1[k] = vy * sn;                                       // the per-image scale goes into the terms: a wave's tiles span images
                 tg[k] = d0[k] * RT_CH(ta, k) + d1[k] * RT_CH(tb, k);
+                if (RT_DEAD(c)) tg[k] = 0.f;
                 ts[k] = d0[k] + d1[k];
             }
             rt_u32x4 oa, ob;
@@ -499,8 +528,9 @@ __global__ __launch_bounds__(256, 2) void scale_residual_bwd_reg_kernel(const fl
         rt_tile_store<C, PW>(T, rt_buf(dz + ((size_t)n * P + p0) * C, (unsigned)rows * C * 2u), lane);
         rt_lds_fence();
     }
-    if (!staged) { for (int i = threadIdx.x; i < C; i += 256) Lg[i] = gamma[i]; __syncthreads(); }   // a wave without tiles
-    rt_write_partials<CL, G>(accg, accs, part + (size_t)blockIdx.x * 2 * C, (float*)smem, wave, lane, [gamma](float a, int c) { return a * gamma[c]; });
+    if (!staged) { for (int i = threadIdx.x; i < C; i += 256) Lg[i] = (!LD || i < Cl) ? gamma[i] : 0.f; __syncthreads(); }   // a wave without tiles
+    if constexpr (LD) rt_write_partials<CL, G>(accg, accs, part + (size_t)blockIdx.x * 2 * C, (float*)smem, wave, lane, [gamma, Cl](float a, int c) { return c < Cl ? a * gamma[c] : 0.f; });
+    else rt_write_partials<CL, G>(accg, accs, part + (size_t)blockIdx.x * 2 * C, (float*)smem, wave, lane, [gamma](float a, int c) { return a * gamma[c]; });
 }
 
 // The backward residual step for SMALL planes, a wave per (image, CW channels, 64 pixel pairs) like scale_residual_fwd_chan_kernel: the
@@ -868,52 +898,54 @@ template <typename K> static int rt_set_lds(K k, size_t lds) {
     return slak_set_max_lds((const void*)k, lds) ? 0 : 1;
 }
 
-template <int CL, int G, bool XF32 = false, bool PATCH = false>
-static int launch_ln_fwd_reg(const void* x, const float* w, const float* b, uint16_t* y, float* mean, float* rstd, int N, int P, float eps, hipStream_t st, int Wimg = 0) {
+template <int CL, int G, bool XF32 = false, bool PATCH = false, bool LD = false>
+static int launch_ln_fwd_reg(const void* x, const float* w, const float* b, uint16_t* y, float* mean, float* rstd, int N, int P, float eps, hipStream_t st, int Wimg = 0,
+                             int Cl = CL * G) {
     using GE = RtGeom<CL, G>;
     const int tpi = (P + GE::PW - 1) / GE::PW, ntiles = N * tpi;
     const size_t lds = (size_t)4 * GE::LDS_WAVE + (size_t)2 * GE::C * sizeof(float);
-    auto k = ln_nchw_to_nhwc_fwd_reg_kernel<CL, G, XF32, PATCH>;
+    auto k = ln_nchw_to_nhwc_fwd_reg_kernel<CL, G, XF32, PATCH, LD>;
     if (rt_set_lds(k, lds)) return SLAK_ERR_LAUNCH;
-    hipLaunchKernelGGL(k, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), lds, st, x, w, b, y, mean, rstd, N, P, eps, tpi, ntiles, Wimg);
+    hipLaunchKernelGGL(k, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), lds, st, x, w, b, y, mean, rstd, N, P, eps, tpi, ntiles, Wimg, Cl);
     SLAK_LAUNCH_CHECK();
     return SLAK_OK;
 }
-template <int CL, int G, bool XF32 = false, bool PATCH = false>
+template <int CL, int G, bool XF32 = false, bool PATCH = false, bool LD = false>
 static int launch_ln_bwd_reg(const uint16_t* g, const void* x, const float* w, const float* mean, const float* rstd, void* dx, float* part,
-                             int* rows, int N, int P, hipStream_t st, int Wimg = 0) {
+                             int* rows, int N, int P, hipStream_t st, int Wimg = 0, int Cl = CL * G) {
     using GE = RtGeom<CL, G>;
     const int tpi = (P + GE::PW - 1) / GE::PW, ntiles = N * tpi;
     const size_t lds = (size_t)4 * GE::LDS_WAVE + (size_t)2 * GE::C * sizeof(float);
-    auto k = ln_nchw_to_nhwc_bwd_reg_kernel<CL, G, XF32, PATCH>;
+    auto k = ln_nchw_to_nhwc_bwd_reg_kernel<CL, G, XF32, PATCH, LD>;
     if (rt_set_lds(k, lds)) return SLAK_ERR_LAUNCH;
     const int grid = rt_persistent_grid(k, lds, ntiles);
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(256), lds, st, g, x, w, mean, rstd, dx, part, N, P, tpi, ntiles, Wimg);
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(256), lds, st, g, x, w, mean, rstd, dx, part, N, P, tpi, ntiles, Wimg, Cl);
     SLAK_LAUNCH_CHECK();
     *rows = grid;
     return SLAK_OK;
 }
-template <int CL, int G, typename Tsc>
-static int launch_sr_fwd_reg(const Tsc* sc, const uint16_t* z, const float* gamma, const float* scale, float* out, uint16_t* out16, int N, int P, hipStream_t st) {
+template <int CL, int G, typename Tsc, bool LD = false>
+static int launch_sr_fwd_reg(const Tsc* sc, const uint16_t* z, const float* gamma, const float* scale, float* out, uint16_t* out16, int N, int P, hipStream_t st,
+                             int Cl = CL * G) {
     using GE = RtGeom<CL, G>;
     const int tpi = (P + GE::PW - 1) / GE::PW, ntiles = N * tpi;
     const size_t lds = (size_t)4 * GE::LDS_WAVE + (size_t)2 * GE::C * sizeof(float);
-    auto k = scale_residual_fwd_reg_kernel<CL, G, Tsc>;
+    auto k = scale_residual_fwd_reg_kernel<CL, G, Tsc, LD>;
     if (rt_set_lds(k, lds)) return SLAK_ERR_LAUNCH;
-    hipLaunchKernelGGL(k, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), lds, st, sc, z, gamma, scale, out, out16, N, P, tpi, ntiles);
+    hipLaunchKernelGGL(k, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), lds, st, sc, z, gamma, scale, out, out16, N, P, tpi, ntiles, Cl);
     SLAK_LAUNCH_CHECK();
     return SLAK_OK;
 }
-template <int CL, int G>
+template <int CL, int G, bool LD = false>
 static int launch_sr_bwd_reg(const float* dout, const uint16_t* dout16, float* dsum, const uint16_t* z, const float* gamma, const float* scale,
-                             uint16_t* dz, float* part, int* rows, int N, int P, hipStream_t st) {
+                             uint16_t* dz, float* part, int* rows, int N, int P, hipStream_t st, int Cl = CL * G) {
     using GE = RtGeom<CL, G>;
     const int tpi = (P + GE::PW - 1) / GE::PW, ntiles = N * tpi;
     const size_t lds = (size_t)4 * GE::LDS_WAVE + (size_t)2 * GE::C * sizeof(float);
-    auto k = scale_residual_bwd_reg_kernel<CL, G>;
+    auto k = scale_residual_bwd_reg_kernel<CL, G, LD>;
     if (rt_set_lds(k, lds)) return SLAK_ERR_LAUNCH;
     const int grid = rt_persistent_grid(k, lds, ntiles);
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(256), lds, st, dout, dout16, dsum, z, gamma, scale, dz, part, N, P, tpi, ntiles);
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(256), lds, st, dout, dout16, dsum, z, gamma, scale, dz, part, N, P, tpi, ntiles, Cl);
     SLAK_LAUNCH_CHECK();
     *rows = grid;
     return SLAK_OK;
@@ -1056,6 +1088,48 @@ int launch_scale_residual_bwd_reg(const float* dout, const void* dout16, float* 
     }
 #define CALL(CL, G) return launch_sr_bwd_reg<CL, G>(dout, (const uint16_t*)dout16, dsum, (const uint16_t*)z, gamma, scale, (uint16_t*)dz, part, rows, N, P, st)
     SLAK_RT_DISPATCH(C, CALL)
+#undef CALL
+}
+
+// ---- the pitched entry points (slak_*_ld): Cl channel rows on the NCHW side, rows of ldc on the NHWC side.  The pixel-pair kernels above on the
+// instantiation whose C IS the pitch (128 / 256 / 512: Cl = 124 / 249 / 499 of the width-1.3 models), even planes, at most RT_LD_PAD pad columns; SLAK_ERR_UNSUPPORTED elsewhere
+// (the caller runs the LDS-tile kernels of block_tail.hip).  The partial rows are 2 * ldc wide: [0, Cl) and [ldc, ldc + Cl) are the logical columns.
+#define SLAK_RT_DISPATCH_LD(LDC, CALL)            \
+    if ((P & 1) || Cl > LDC || LDC - Cl > RT_LD_PAD) return SLAK_ERR_UNSUPPORTED; \
+    switch (LDC) {                                \
+        case 128: { CALL(64, 2); }                \
+        case 256: { CALL(64, 4); }                \
+        case 512: { CALL(64, 8); }                \
+        default: return SLAK_ERR_UNSUPPORTED;     \
+    }
+int launch_ln_nchw_to_nhwc_fwd_reg_ld(const void* x, const float* w, const float* b, void* y, float* mean, float* rstd, int N, int Cl, int ldc, int P, float eps, hipStream_t st) {
+#define CALL(CL, G) return (launch_ln_fwd_reg<CL, G, false, false, true>((const uint16_t*)x, w, b, (uint16_t*)y, mean, rstd, N, P, eps, st, 0, Cl))
+    SLAK_RT_DISPATCH_LD(ldc, CALL)
+#undef CALL
+}
+int launch_ln_nchw_to_nhwc_bwd_reg_ld(const void* g, const void* x, const float* w, const float* mean, const float* rstd, void* dx, float* part, int* rows,
+                                      int N, int Cl, int ldc, int P, hipStream_t st) {
+#define CALL(CL, G) return (launch_ln_bwd_reg<CL, G, false, false, true>((const uint16_t*)g, (const uint16_t*)x, w, mean, rstd, (uint16_t*)dx, part, rows, N, P, st, 0, Cl))
+    SLAK_RT_DISPATCH_LD(ldc, CALL)
+#undef CALL
+}
+int launch_scale_residual_fwd_reg_ld(const void* sc, int sc_dtype, const void* z, const float* gamma, const float* scale, float* out, void* out16,
+                                     int N, int Cl, int ldc, int P, hipStream_t st) {
+    if (sc_dtype == SLAK_F32) {
+#define CALL(CL, G) return (launch_sr_fwd_reg<CL, G, float, true>((const float*)sc, (const uint16_t*)z, gamma, scale, out, (uint16_t*)out16, N, P, st, Cl))
+        SLAK_RT_DISPATCH_LD(ldc, CALL)
+#undef CALL
+    } else if (sc_dtype == SLAK_BF16) {
+#define CALL(CL, G) return (launch_sr_fwd_reg<CL, G, bf16_t, true>((const bf16_t*)sc, (const uint16_t*)z, gamma, scale, out, (uint16_t*)out16, N, P, st, Cl))
+        SLAK_RT_DISPATCH_LD(ldc, CALL)
+#undef CALL
+    }
+    return SLAK_ERR_UNSUPPORTED;
+}
+int launch_scale_residual_bwd_reg_ld(const float* dout, const void* dout16, float* dsum, const void* z, const float* gamma, const float* scale, void* dz,
+                                     float* part, int* rows, int N, int Cl, int ldc, int P, hipStream_t st) {
+#define CALL(CL, G) return (launch_sr_bwd_reg<CL, G, true>(dout, (const uint16_t*)dout16, dsum, (const uint16_t*)z, gamma, scale, (uint16_t*)dz, part, rows, N, P, st, Cl))
+    SLAK_RT_DISPATCH_LD(ldc, CALL)
 #undef CALL
 }
 

@@ -266,6 +266,14 @@ int launch_scale_residual_fwd_reg(const void* sc, int sc_dtype, const void* z, c
                                   int N, int C, int P, hipStream_t st);
 int launch_scale_residual_bwd_reg(const float* dout, const void* dout16, float* dsum, const void* z, const float* gamma, const float* scale, void* dz,
                                   float* part, int* rows, int N, int C, int P, hipStream_t st);
+// ... and the same kernels for the pitched entry points: Cl channel rows on the NCHW side, rows of ldc (128 / 256 / 512) on the NHWC side; partial rows [rows][2 ldc]
+int launch_ln_nchw_to_nhwc_fwd_reg_ld(const void* x, const float* w, const float* b, void* y, float* mean, float* rstd, int N, int Cl, int ldc, int P, float eps, hipStream_t st);
+int launch_ln_nchw_to_nhwc_bwd_reg_ld(const void* g, const void* x, const float* w, const float* mean, const float* rstd, void* dx, float* part, int* rows,
+                                      int N, int Cl, int ldc, int P, hipStream_t st);
+int launch_scale_residual_fwd_reg_ld(const void* sc, int sc_dtype, const void* z, const float* gamma, const float* scale, float* out, void* out16,
+                                     int N, int Cl, int ldc, int P, hipStream_t st);
+int launch_scale_residual_bwd_reg_ld(const float* dout, const void* dout16, float* dsum, const void* z, const float* gamma, const float* scale, void* dz,
+                                     float* part, int* rows, int N, int Cl, int ldc, int P, hipStream_t st);
 // linear_wgrad.hip: D[N1][N2] (fp32) = X1^T X2 over M rows (the pointwise Linear weight gradient)
 bool linear_wgrad_supported(int M, int N1, int N2);
 size_t linear_wgrad_workspace(int M, int N1, int N2);

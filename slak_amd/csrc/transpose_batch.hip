@@ -82,6 +82,41 @@ __global__ __launch_bounds__(256) void nchw_to_pixel_major_kernel(const uint16_t
     }
 }
 
+// dst = bf16(src), zero-padded to [drows][dcols] and optionally transposed, for many fp32 matrices in one launch: the zero-padded bf16 weight
+// copies the pointwise GEMMs of a pitched block read (block_tail.hip, slak_*_ld; slak_amd/block_ops.py keeps them by the parameter's version).
+// tr == 0: dst[r][c] = src[r][c] inside [rows][cols], 0 elsewhere; tr == 1: dst[r][c] = src[c][r] inside [cols][rows], 0 elsewhere.
+// A workgroup owns one 64 x 64 tile of dst; source rows are only 4-byte aligned (cols = 249): plain loads, coalesced on both sides (through LDS
+// when transposing).
+constexpr int PCB_MAX = 64;
+struct PcbJobs { const float* src[PCB_MAX]; uint16_t* dst[PCB_MAX]; int rows[PCB_MAX], cols[PCB_MAX], drows[PCB_MAX], dcols[PCB_MAX], tr[PCB_MAX], tile0[PCB_MAX + 1]; int n; };
+
+__global__ __launch_bounds__(256) void pad_cast_batch_kernel(const PcbJobs jobs) {
+    __shared__ uint16_t tile[64][64 + 2];
+    int j = 0;
+    while (j + 1 < jobs.n && (int)blockIdx.x >= jobs.tile0[j + 1]) ++j;
+    const int rows = jobs.rows[j], cols = jobs.cols[j], drows = jobs.drows[j], dcols = jobs.dcols[j];
+    const int tcs = (dcols + 63) / 64, tl = (int)blockIdx.x - jobs.tile0[j];
+    const int r0 = (tl / tcs) * 64, c0 = (tl % tcs) * 64;              // the tile's origin in dst
+    const float* __restrict__ src = jobs.src[j];
+    uint16_t* __restrict__ dst = jobs.dst[j];
+    if (!jobs.tr[j]) {
+        for (int i = threadIdx.x; i < 64 * 64; i += 256) {
+            const int r = r0 + (i >> 6), c = c0 + (i & 63);
+            if (r < drows && c < dcols) dst[(size_t)r * dcols + c] = (r < rows && c < cols) ? f32_to_bf16_bits(src[(size_t)r * cols + c]) : (uint16_t)0;
+        }
+        return;
+    }
+    for (int i = threadIdx.x; i < 64 * 64; i += 256) {                  // source row = dst column, source column = dst row
+        const int sr = c0 + (i >> 6), sc = r0 + (i & 63);
+        tile[i >> 6][i & 63] = (sr < rows && sc < cols) ? f32_to_bf16_bits(src[(size_t)sr * cols + sc]) : (uint16_t)0;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 64 * 64; i += 256) {
+        const int r = r0 + (i >> 6), c = c0 + (i & 63);
+        if (r < drows && c < dcols) dst[(size_t)r * dcols + c] = tile[i & 63][i >> 6];
+    }
+}
+
 }  // namespace slak
 
 using namespace slak;
@@ -119,6 +154,32 @@ int slak_nchw_to_pixel_major_bf16(const void* src, void* dst, int N, int C, int 
     else if (P % 4 == 0) hipLaunchKernelGGL(nchw_to_pixel_major_kernel<4>, grid, dim3(256), 0, st, (const uint16_t*)src, (uint16_t*)dst, C, P);
     else hipLaunchKernelGGL(nchw_to_pixel_major_kernel<1>, grid, dim3(256), 0, st, (const uint16_t*)src, (uint16_t*)dst, C, P);
     SLAK_LAUNCH_CHECK();
+    return SLAK_OK;
+}
+
+int slak_pad_cast_bf16_batch(const void* const* src_f32, void* const* dst_bf16, const int* rows, const int* cols, const int* dst_rows, const int* dst_cols,
+                             const int* transpose, int n, void* stream) {
+    if (n <= 0) return SLAK_OK;
+    if (!src_f32 || !dst_bf16 || !rows || !cols || !dst_rows || !dst_cols || !transpose) return SLAK_ERR_INVALID_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    for (int b = 0; b < n; b += PCB_MAX) {
+        PcbJobs jobs;
+        jobs.n = n - b < PCB_MAX ? n - b : PCB_MAX;
+        long long t = 0;
+        for (int i = 0; i < jobs.n; ++i) {
+            const int k = b + i, tr = transpose[k] ? 1 : 0;
+            if (!src_f32[k] || !dst_bf16[k] || rows[k] <= 0 || cols[k] <= 0) return SLAK_ERR_INVALID_ARG;
+            if (dst_rows[k] < (tr ? cols[k] : rows[k]) || dst_cols[k] < (tr ? rows[k] : cols[k])) return SLAK_ERR_INVALID_ARG;
+            jobs.src[i] = (const float*)src_f32[k]; jobs.dst[i] = (uint16_t*)dst_bf16[k];
+            jobs.rows[i] = rows[k]; jobs.cols[i] = cols[k]; jobs.drows[i] = dst_rows[k]; jobs.dcols[i] = dst_cols[k]; jobs.tr[i] = tr;
+            jobs.tile0[i] = (int)t;
+            t += (long long)((dst_rows[k] + 63) / 64) * ((dst_cols[k] + 63) / 64);
+            if (t >= (1LL << 30)) return SLAK_ERR_UNSUPPORTED;
+        }
+        jobs.tile0[jobs.n] = (int)t;
+        hipLaunchKernelGGL(pad_cast_batch_kernel, dim3((unsigned)t), dim3(256), 0, st, jobs);
+        SLAK_LAUNCH_CHECK();
+    }
     return SLAK_OK;
 }
 

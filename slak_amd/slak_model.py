@@ -199,6 +199,11 @@ class ReparamLargeKernelConv(nn.Module):
             del self.small_conv
 
 
+def _nhwc_pitch(C):
+    from . import block_ops
+    return block_ops.nhwc_pitch(C)
+
+
 class Block(nn.Module):
     """dw large-kernel -> LN (channels_last) -> Linear(C,4C) -> GELU -> Linear(4C,C) -> gamma -> residual."""
 
@@ -227,9 +232,10 @@ class Block(nn.Module):
                 return r
         shortcut = x
         x = self.large_kernel(x, lowp=x_lowp)
-        # the fused tail kernels take even C <= 1024 (tail_args_ok in csrc/block_tail.hip); anything else runs the PyTorch ops below
+        # the fused tail kernels take C <= 1024 (even C: the plain entry points; odd C: NHWC rows of pitch block_ops.nhwc_pitch(C), slak_*_ld in
+        # csrc/block_tail.hip); anything else runs the PyTorch ops below
         if (self.fused_tail and x.is_cuda and x.dtype == torch.bfloat16 and self.gamma is not None
-                and x.shape[1] % 2 == 0 and x.shape[1] <= 1024):
+                and _nhwc_pitch(x.shape[1]) is not None):
             r = self._forward_fused_tail(shortcut, x)
             return r if isinstance(r, tuple) else (r, None)
         self.__dict__.pop("_pending_scale", None)               # drawn for the fused tail only
@@ -268,7 +274,11 @@ def _block_forward_fused_tail(self, shortcut, x):
     """Same arithmetic as the lines below it in Block.forward, with the permute/LayerNorm and gamma/permute/residual steps as
     one HIP kernel each (slak_amd/block_ops.py); the two Linear layers and GELU are unchanged."""
     from . import block_ops
-    t = block_ops.ln_nchw_to_nhwc(x.contiguous(), self.norm.weight.float(), self.norm.bias.float(), self.norm.eps)
+    ldc = block_ops.nhwc_pitch(x.shape[1])
+    if ldc == x.shape[1]:
+        t = block_ops.ln_nchw_to_nhwc(x.contiguous(), self.norm.weight.float(), self.norm.bias.float(), self.norm.eps)
+    else:                                                        # odd C (or pad_even_widths): pitched rows, mlp_scale_residual reads the pitch off t
+        t = block_ops.ln_nchw_to_nhwc_pitched(x.contiguous(), self.norm.weight.float(), self.norm.bias.float(), self.norm.eps, ldc)
     scale = None
     dp = self.drop_path
     if isinstance(dp, DropPath) and dp.drop_prob > 0.0 and self.training:
@@ -293,7 +303,7 @@ def _block_forward_fused_block(self, x, x_lowp):
     if not (self.fused_tail and lk.fused_bn and lk.fused_tri and lk.Decom and lk.lowp_dwconv and self.gamma is not None
             and hasattr(lk, "small_conv") and hasattr(lk, "LoRA1") and hasattr(lk.LoRA1, "bn")
             and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16
-            and x.dim() == 4 and x.dtype in (torch.float32, torch.bfloat16) and x.shape[1] % 2 == 0 and x.shape[1] <= 1024):
+            and x.dim() == 4 and x.dtype in (torch.float32, torch.bfloat16) and _nhwc_pitch(x.shape[1]) is not None):
         return None
     c1, c2, c3 = lk.LoRA1.conv, lk.LoRA2.conv, lk.small_conv.conv
     bns = (lk.LoRA1.bn, lk.LoRA2.bn, lk.small_conv.bn)

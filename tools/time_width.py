@@ -1,0 +1,99 @@
+"""Step time of SLaK-T at a width factor (default 1.3: the width of every README recipe, C = 124 / 249 / 499 / 998), with bench.py's protocol:
+
+    python tools/time_width.py [--width 1.3] [--batch 128] [--res 224] [--steps 20] [--warmup 5] [--prime 15]
+
+224 px, bf16 autocast, batch 128, MaskedAdamW, every fused path bench.py turns on; prime + warm-up steps, then K steps between two
+synchronisations.  Prints ONE JSON line: ms_per_step, host_enqueue_ms_per_step (three steps enqueued on a drained queue, the quietest of three
+rounds) and pitched_block_hits (block forwards that ran on pitched NHWC tensors: 0 on a tree without them, and at width 1.0).
+SLAK_PAD_EVEN=1 also pads the even widths 124 / 998 (block_ops.pad_even_widths).  bench.py itself has no width switch.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+import torch
+import torch.nn as nn
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--width", type=float, default=1.3)
+    ap.add_argument("--batch", type=int, default=128)
+    ap.add_argument("--res", type=int, default=224)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--prime", type=int, default=15)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("tools/time_width.py needs an MI355X (no CPU fallback for the hot path)")
+    device = torch.device("cuda", 0)
+    torch.cuda.set_device(0)
+    torch.backends.cudnn.benchmark = True
+    import slak_amd.slak_model as M
+    from slak_amd import block_ops
+    from slak_amd.optim_factory import MaskedAdamW
+    M.Block.fused_tail = True
+    M.ReparamLargeKernelConv.fused_bn = True
+    M.LayerNorm.fused_cf = True
+    M.SLaK.fused_stem = True
+    M.SLaK.fused_downsample = True
+    M.ReparamLargeKernelConv.fused_tri = True
+    M.Block.fused_block = True
+    block_ops.cache_lowp_weights = True
+    M.use_sync_bn = True
+    torch.manual_seed(0)
+    model = M.create_model("SLaK_tiny", kernel_size=[51, 49, 47, 13, 5], Decom=True, bn=True, drop_path_rate=0.1, lowp_dwconv=True,
+                           width_factor=a.width).to(device)
+    decay, no_decay = [], []
+    for n, p in model.named_parameters():
+        (no_decay if (p.dim() == 1 or n.endswith(".bias")) else decay).append(p)
+    opt = MaskedAdamW([dict(params=decay, weight_decay=0.05), dict(params=no_decay, weight_decay=0.0)], lr=4e-3)
+    criterion = nn.CrossEntropyLoss(label_smoothing=0.1)
+    g = torch.Generator(device=device).manual_seed(1234)
+    samples = torch.randn(a.batch, 3, a.res, a.res, device=device, generator=g)
+    targets = torch.randint(0, 1000, (a.batch,), device=device, generator=g)
+
+    def step():
+        with torch.autocast("cuda", dtype=torch.bfloat16):
+            loss = criterion(model(samples), targets)
+        loss.backward()
+        opt.step()
+        opt.zero_grad(set_to_none=True)
+        return loss
+
+    model.train()
+    for _ in range(a.prime + a.warmup):
+        loss = step()
+    torch.cuda.synchronize()
+    hits0 = getattr(block_ops, "pitched_block_hits", 0)
+    t0 = time.perf_counter()
+    for _ in range(a.steps):
+        loss = step()
+    torch.cuda.synchronize()
+    elapsed = time.perf_counter() - t0
+    hits = getattr(block_ops, "pitched_block_hits", 0) - hits0
+    host = float("inf")
+    for _ in range(3):
+        h0 = time.perf_counter()
+        for _ in range(3):
+            step()
+        host = min(host, (time.perf_counter() - h0) / 3)
+        torch.cuda.synchronize()
+    dims = [int(d * a.width) for d in (96, 192, 384, 768)]
+    print(json.dumps({"workload": "SLaK-T 51x51, width_factor %g (C = %s), bs=%d, %dx%d, bf16, MaskedAdamW" % (a.width, dims, a.batch, a.res, a.res),
+                      "ms_per_step": round(1e3 * elapsed / a.steps, 4), "host_enqueue_ms_per_step": round(1e3 * host, 3),
+                      "pitched_block_hits": int(hits), "pitched_block_hits_per_step": hits / max(1, a.steps),
+                      "pad_even_widths": bool(getattr(block_ops, "pad_even_widths", False)),
+                      "nhwc_pitch": [block_ops.nhwc_pitch(c) if hasattr(block_ops, "nhwc_pitch") else None for c in dims],
+                      "block_runner": bool(block_ops._runner() is not None), "steps": a.steps, "warmup": a.warmup, "prime": a.prime,
+                      "final_loss": float(loss.item()), "gpu": torch.cuda.get_device_name(0)}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
