@@ -175,8 +175,9 @@ int slak_dwconv2d_forward_stats(const void* x, int x_dtype, const void* w, int w
                                 int* stats_rows, int N, int C, int H, int W, int kh, int kw, void* stream);
 /* slak_dwconv2d_tri_forward that also leaves the batch statistics of the three branch BatchNorms (models/SLaK.py:92-95: conv -> bn per
  * branch): stats[rows][C][6] = partial sums (sum y_v, sum y_v^2, sum y_h, sum y_h^2, sum y_s, sum y_s^2) of the STORED (rounded) outputs per
- * (row, channel); rows = slak_dwconv2d_tri_stats_rows(...) (0: no such kernel for the shape; bf16 only).  slak_bn3_forward_local takes them in
- * place of its own pass over the three tensors. */
+ * (row, channel); rows = slak_dwconv2d_tri_stats_rows(...) (0: no such kernel for the shape; bf16 only; maps beyond 64, where
+ * slak_dwconv2d_tri_forward runs the wide kernel, have none: 0 rows and SLAK_ERR_UNSUPPORTED).  slak_bn3_forward_local takes them in place of
+ * its own pass over the three tensors. */
 int slak_dwconv2d_tri_stats_rows(int dtype, int N, int C, int H, int W, int K);
 int slak_dwconv2d_tri_forward_stats(const void* x, const float* w_v, const float* w_h, const float* w_s, void* y_v, void* y_h, void* y_s,
                                     float* stats, int dtype, int N, int C, int H, int W, int K, void* stream);

@@ -5,6 +5,7 @@
 
 (models/SLaK.py:153-166, :253-255).  x bf16 NCHW, z bf16 NHWC; parameters, statistics and the residual stream fp32.
 """
+import collections
 import ctypes
 import os
 
@@ -204,20 +205,22 @@ fused_tri_backward = os.environ.get("SLAK_TRI_BACKWARD", "1") != "0"   # A/B swi
 
 
 _tri_plan_cache = {}
+# one-launch forward?  one-launch data gradient?  rows of the forward launch's BatchNorm statistics; workspace bytes of the three-branch weight
+# gradient and of the two-branch one (0: no such launch); data gradient + the three weight gradients in one launch?
+_TriPlan = collections.namedtuple("_TriPlan", "forward dgrad stats_rows tri_wgrad_bytes pair_wgrad_bytes backward")
+_NO_TRI_PLAN = _TriPlan(False, False, 0, 0, 0, False)
 
 
 def _tri_plan(dt, N, C, H, W, K):
-    """What the library answers for a block shape -- (one-launch forward?, one-launch data gradient?, rows of the forward launch's BatchNorm
-    statistics, workspace bytes of the three-branch weight gradient, of the two-branch one, one-launch backward?) -- asked once per (dtype,
-    shape): six ctypes calls per block and direction otherwise."""
+    """What the library answers for a block shape, asked once per (dtype, shape): six ctypes calls per block and direction otherwise."""
     key = (dt, N, C, H, W, K)
     plan = _tri_plan_cache.get(key)
     if plan is None:
         L = _lib.lib()
-        plan = (L.slak_dwconv2d_tri_supported_op(dt, N, C, H, W, K, 0) == 1, L.slak_dwconv2d_tri_supported_op(dt, N, C, H, W, K, 1) == 1,
-                int(L.slak_dwconv2d_tri_stats_rows(dt, N, C, H, W, K)), int(L.slak_dwconv2d_tri_filter_workspace_bytes(dt, N, C, H, W, K)),
-                int(L.slak_dwconv2d_pair_filter_workspace_bytes(dt, N, C, H, W, K)),
-                L.slak_dwconv2d_tri_backward_supported(dt, N, C, H, W, K) == 1)      # [5]: data gradient + the three weight gradients in one launch
+        plan = _TriPlan(L.slak_dwconv2d_tri_supported_op(dt, N, C, H, W, K, 0) == 1, L.slak_dwconv2d_tri_supported_op(dt, N, C, H, W, K, 1) == 1,
+                        int(L.slak_dwconv2d_tri_stats_rows(dt, N, C, H, W, K)), int(L.slak_dwconv2d_tri_filter_workspace_bytes(dt, N, C, H, W, K)),
+                        int(L.slak_dwconv2d_pair_filter_workspace_bytes(dt, N, C, H, W, K)),
+                        L.slak_dwconv2d_tri_backward_supported(dt, N, C, H, W, K) == 1)
         _tri_plan_cache[key] = plan
     return plan
 
@@ -235,12 +238,12 @@ def _tri_forward_impl(x, wv, wh, ws, want_stats):
     dt = ops._DT.get(x.dtype)
     # one launch for the three branches where the library says it wins (slak_dwconv2d_tri_supported_op: per op)
     f32w = all(w.dtype == torch.float32 and w.is_contiguous() for w in (wv, wh, ws))
-    plan = _tri_plan(dt, N, C, H, W, K) if (dt is not None and f32w) else (False, False, 0, 0, 0, False)
-    tri, tri_dgrad = plan[0], plan[1]
+    plan = _tri_plan(dt, N, C, H, W, K) if (dt is not None and f32w) else _NO_TRI_PLAN
+    tri, tri_dgrad = plan.forward, plan.dgrad
     stats = None
     if tri:
         yv, yh, ys = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
-        rows = plan[2] if (want_stats == 2 and bn_stats_in_conv) else 0
+        rows = plan.stats_rows if (want_stats == 2 and bn_stats_in_conv) else 0
         with _on(x.device):
             if rows > 0:                                     # the launch also leaves the branch BatchNorms' batch statistics
                 stats = torch.empty((rows, C, 6), dtype=torch.float32, device=x.device)
@@ -268,14 +271,14 @@ def _tri_backward_impl(x, wv, wh, ws, dyv, dyh, dys, tri_dgrad, need_dx, need_w)
     dyv, dyh, dys = (torch.zeros_like(x) if g is None else g for g in (dyv, dyh, dys))       # (a branch output nobody used)
     dyv, dyh, dys = (g.contiguous() if g.dtype == x.dtype else g.to(x.dtype).contiguous() for g in (dyv, dyh, dys))
     dx = None
-    plan = _tri_plan(ops._DT[x.dtype], N, C, H, W, K) if x.dtype in ops._DT else (False, False, 0, 0, 0, False)
-    if need_dx and all(need_w) and fused_tri_wgrad and fused_tri_backward and plan[5] and plan[3] and \
+    plan = _tri_plan(ops._DT[x.dtype], N, C, H, W, K) if x.dtype in ops._DT else _NO_TRI_PLAN
+    if need_dx and all(need_w) and fused_tri_wgrad and fused_tri_backward and plan.backward and plan.tri_wgrad_bytes and \
             all(w.dtype == torch.float32 and w.is_contiguous() for w in (wv, wh, ws)):
         # the whole backward in ONE launch (14 x 14 class): the dY planes are staged once for dx and for the three weight gradients
         L = _lib.lib()
         dx = torch.empty_like(x)
         dwv, dwh, dws = (torch.empty_like(w, dtype=torch.float32) for w in (wv, wh, ws))
-        wsb, nbb = _workspace(plan[3], x.device)
+        wsb, nbb = _workspace(plan.tri_wgrad_bytes, x.device)
         with _on(x.device):
             rc = L.slak_dwconv2d_tri_backward(dyv.data_ptr(), dyh.data_ptr(), dys.data_ptr(), x.data_ptr(), wv.data_ptr(), wh.data_ptr(), ws.data_ptr(),
                                               dx.data_ptr(), dwv.data_ptr(), dwh.data_ptr(), dws.data_ptr(), ops._DT[x.dtype], N, C, H, W, K,
@@ -301,11 +304,11 @@ def _tri_backward_impl(x, wv, wh, ws, dyv, dyh, dys, tri_dgrad, need_dx, need_w)
                 dx += ops.dwconv2d_backward_data(dyh, wh)
                 dx += ops.dwconv2d_backward_data(dys, ws)
     dwv = dwh = dws = None
-    if all(need_w) and fused_tri_wgrad and plan[3]:          # one launch for the three weight gradients (x fetched once)
+    if all(need_w) and fused_tri_wgrad and plan.tri_wgrad_bytes:          # one launch for the three weight gradients (x fetched once)
         L = _lib.lib()
         dt = ops._DT[x.dtype]
         dwv, dwh, dws = (torch.empty_like(w, dtype=torch.float32) for w in (wv, wh, ws))
-        wsb, nbb = _workspace(plan[3], x.device)
+        wsb, nbb = _workspace(plan.tri_wgrad_bytes, x.device)
         with _on(x.device):
             rc = L.slak_dwconv2d_tri_backward_filter(dyv.data_ptr(), dyh.data_ptr(), dys.data_ptr(), x.data_ptr(), dwv.data_ptr(),
                                                      dwh.data_ptr(), dws.data_ptr(), dt, N, C, H, W, K, wsb.data_ptr(), nbb, _stream(x.device))
@@ -313,11 +316,11 @@ def _tri_backward_impl(x, wv, wh, ws, dyv, dyh, dys, tri_dgrad, need_dx, need_w)
             dwv = dwh = dws = None
         else:
             _lib.check(rc, "slak_dwconv2d_tri_backward_filter")
-    if dwv is None and need_w[0] and need_w[2] and fused_tri_wgrad and plan[4]:      # K x 5 and 5 x 5 in one launch (x fetched and shifted once)
+    if dwv is None and need_w[0] and need_w[2] and fused_tri_wgrad and plan.pair_wgrad_bytes:      # K x 5 and 5 x 5 in one launch (x fetched and shifted once)
         L = _lib.lib()
         dt = ops._DT[x.dtype]
         dwv, dws = (torch.empty_like(w, dtype=torch.float32) for w in (wv, ws))
-        wsb, nbb = _workspace(plan[4], x.device)
+        wsb, nbb = _workspace(plan.pair_wgrad_bytes, x.device)
         with _on(x.device):
             rc = L.slak_dwconv2d_pair_backward_filter(dyv.data_ptr(), dys.data_ptr(), x.data_ptr(), dwv.data_ptr(), dws.data_ptr(),
                                                       dt, N, C, H, W, K, wsb.data_ptr(), nbb, _stream(x.device))

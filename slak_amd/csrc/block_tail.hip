@@ -1257,10 +1257,7 @@ size_t slak_block_tail_workspace_bytes(int N, int C, int P) {
     return align_up((rows + BT_SLICES) * 2 * C * sizeof(float), 256);
 }
 
-static bool tail_use_reg() {                  // SLAK_TAIL_REG=0 keeps the LDS-tile kernels (A/B testing)
-    static const bool v = [] { const char* e = getenv("SLAK_TAIL_REG"); return !(e && e[0] == '0'); }();
-    return v;
-}
+static bool tail_use_reg() { static const bool v = slak_env_flag("SLAK_TAIL_REG", true); return v; }   // SLAK_TAIL_REG=0 keeps the LDS-tile kernels (A/B testing)
 static int tail_args_ok(int N, int C, int P) {
     if (N <= 0 || C <= 0 || P <= 0) return SLAK_ERR_INVALID_ARG;
     if ((C & 1) || C > 1024) return SLAK_ERR_UNSUPPORTED;
@@ -1656,7 +1653,7 @@ int slak_ln_channels_first_forward_pair(const void* x, int x_dtype, const float*
 // the one-pass kernel (64-pixel tiles, the waves split the channels, a lane's share in registers): bf16 x, fp32 g, C = 96 / 128 / 192 (the stems of
 // SLaK-T/S, -B and -L)
 static bool cf_reg_covers(int g_dtype, int x_dtype, int N, int C, int P) {
-    static const bool off = [] { const char* e = getenv("SLAK_LN_CF_REG"); return e && atoi(e) == 0; }();
+    static const bool off = !slak_env_flag("SLAK_LN_CF_REG", true);
     (void)N; (void)P;
     return !off && g_dtype == SLAK_F32 && x_dtype == SLAK_BF16 && (C == 96 || C == 128 || C == 192);
 }

@@ -955,10 +955,7 @@ static int rt_chan_max_p() {                 // largest plane (pixels) the chann
     static const int v = [] { const char* e = slak_dev_getenv("SLAK_RT_CHAN_MAXP"); const int x = e ? atoi(e) : 0; return x > 0 ? x : 256; }();
     return v;
 }
-static bool rt_chan_waves() {                // SLAK_RT_CHAN=0: small planes keep the pixel-tile residual kernel (A/B testing)
-    static const bool v = [] { const char* e = getenv("SLAK_RT_CHAN"); return !(e && e[0] == '0'); }();
-    return v;
-}
+static bool rt_chan_waves() { static const bool v = slak_env_flag("SLAK_RT_CHAN", true); return v; }   // SLAK_RT_CHAN=0: small planes keep the pixel-tile residual kernel (A/B testing)
 template <int CW>
 static int launch_sr_fwd_chan(const float* sc, const uint16_t* z, const float* gamma, const float* scale, float* out, uint16_t* out16, int N, int C, int P, hipStream_t st) {
     const int rounds = (P / 2 + 63) / 64, nunits = N * (C / CW) * rounds;
@@ -999,10 +996,7 @@ static int rt_ln_chan_cw(int C, int P, int N) {
     if (C % 64 == 0 && C / 64 <= 8) return 64;
     return 0;
 }
-static bool rt_wide_lanes() {                // SLAK_RT_WIDE=0: C = 384 keeps 48 channels per lane on 8 lanes per pixel pair (A/B testing)
-    static const bool v = [] { const char* e = getenv("SLAK_RT_WIDE"); return !(e && e[0] == '0'); }();
-    return v;
-}
+static bool rt_wide_lanes() { static const bool v = slak_env_flag("SLAK_RT_WIDE", true); return v; }   // SLAK_RT_WIDE=0: C = 384 keeps 48 channels per lane on 8 lanes per pixel pair (A/B testing)
 // The instantiations: (channels per lane, lanes per pixel) per channel count.  SLAK_ERR_UNSUPPORTED = none for this C (the caller
 // runs the LDS-tile kernels of block_tail.hip).
 #define SLAK_RT_DISPATCH(C, CALL)                 \

@@ -540,10 +540,7 @@ __global__ __launch_bounds__(MF_THREADS) void dwconv_mfma_small_quad_kernel(cons
     }
 }
 
-static bool quad_enabled() {                   // SLAK_SMALL_QUAD=0 keeps the one-plane-per-tile kernel on 7 x 7 (A/B testing)
-    static const bool v = [] { const char* e = getenv("SLAK_SMALL_QUAD"); return !(e && e[0] == '0'); }();
-    return v;
-}
+static bool quad_enabled() { static const bool v = slak_env_flag("SLAK_SMALL_QUAD", true); return v; }   // SLAK_SMALL_QUAD=0 keeps the one-plane-per-tile kernel on 7 x 7 (A/B testing)
 static int quad_target_wgs() {                 // workgroups the launch aims at (dev: SLAK_SQ_WGS per CU)
     static const int wgs_per_cu = [] { const char* e = slak_dev_getenv("SLAK_SQ_WGS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 4; }();
     return wgs_per_cu * mfma_cu_count();

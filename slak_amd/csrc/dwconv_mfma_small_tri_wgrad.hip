@@ -676,10 +676,7 @@ __global__ __launch_bounds__(MF_THREADS) void dwconv_mfma_small_quad_wgrad_kerne
     }
 }
 
-static bool quad_wgrad_enabled() {             // SLAK_SMALL_QUAD=0 keeps the plane-pair kernel on 7 x 7 (A/B testing)
-    static const bool v = [] { const char* e = getenv("SLAK_SMALL_QUAD"); return !(e && e[0] == '0'); }();
-    return v;
-}
+static bool quad_wgrad_enabled() { static const bool v = slak_env_flag("SLAK_SMALL_QUAD", true); return v; }   // SLAK_SMALL_QUAD=0 keeps the plane-pair kernel on 7 x 7 (A/B testing)
 
 // ------------------------------------------------------------------------------------------------------------
 static bool fill_stw_params(SmallTriWgradParams& p, int N, int C, int H, int W, int K, int target_wgs) {
@@ -759,7 +756,7 @@ int launch_dwconv_mfma_small_tri_wgrad(const void* const* dy, const void* x, flo
 
 // The whole backward of a block's three depthwise convs in one launch (14 x 14 class): dx and the three weight gradients.
 bool dwconv_mfma_small_tri_bwd_supported(int N, int C, int H, int W, int K, int dtype) {
-    static const bool on = [] { const char* e = getenv("SLAK_SMALL_TRI_BWD"); return !(e && e[0] == '0'); }();
+    static const bool on = slak_env_flag("SLAK_SMALL_TRI_BWD", true);
     return on && dwconv_mfma_small_tri_wgrad_supported(N, C, H, W, K, dtype) && W >= 8 && !(H <= 7 && W <= 7);
 }
 

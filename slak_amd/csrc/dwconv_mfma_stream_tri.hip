@@ -347,7 +347,7 @@ static size_t stream_lds_bytes(const TeamParams& p) {
 }
 
 bool dwconv_mfma_stream_tri_supported(int N, int C, int H, int W, int K, int dtype) {
-    static const bool off = [] { const char* e = getenv("SLAK_STREAM_TRI"); return e && e[0] == '0'; }();
+    static const bool off = !slak_env_flag("SLAK_STREAM_TRI", true);
     if (off) return false;
     if (dtype != SLAK_BF16 && dtype != SLAK_F16) return false;
     if (N <= 0 || C <= 0 || (long long)N * C * H * W >= (1LL << 30)) return false;

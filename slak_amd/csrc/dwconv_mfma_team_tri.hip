@@ -572,7 +572,7 @@ static bool team_pick_ring(TeamParams& p, int cls) {
 }
 
 bool dwconv_mfma_team_tri_supported(int N, int C, int H, int W, int K, int dtype, bool dgrad) {
-    static const bool off = [] { const char* e = getenv("SLAK_TEAM_TRI"); return e && e[0] == '0'; }();
+    static const bool off = !slak_env_flag("SLAK_TEAM_TRI", true);
     if (off) return false;
     if (dtype != SLAK_BF16 && dtype != SLAK_F16) return false;
     if (N <= 0 || C <= 0 || (long long)N * C * H * W >= (1LL << 30)) return false;       // byte offsets stay below TT_OOB

@@ -428,10 +428,7 @@ __global__ __launch_bounds__(MF_THREADS, 1) void dwconv_mfma_tri_wgrad_rows_kern
 }
 
 // ------------------------------------------------------------------------------------------------------------
-static bool tri_rows_enabled() {               // SLAK_TRI_ROWS=0: the 2 x 2-tile planes keep the two-launch weight gradient (A/B testing)
-    static const bool v = [] { const char* e = getenv("SLAK_TRI_ROWS"); return !(e && e[0] == '0'); }();
-    return v;
-}
+static bool tri_rows_enabled() { static const bool v = slak_env_flag("SLAK_TRI_ROWS", true); return v; }   // SLAK_TRI_ROWS=0: the 2 x 2-tile planes keep the two-launch weight gradient (A/B testing)
 
 static bool fill_tri_rows_params(TriRowsParams& p, int N, int C, int H, int W, int K, int wgs) {
     p.N = N; p.C = C; p.H = H; p.W = W; p.K = K; p.padL = K / 2;
@@ -538,7 +535,7 @@ int launch_dwconv_mfma_tri_wgrad_rows(const void* const* dy, const void* x, floa
     if (!p.counters) return SLAK_ERR_UNSUPPORTED;
     const bool bf = dtype == SLAK_BF16;
     // small branch on the diagonal tiles (see the kernel): four k-steps and a second X tile that reaches back to row 30 or further
-    static const bool sd_on = [] { const char* e = getenv("SLAK_TRI_ROWS_SD"); return !(e && e[0] == '0'); }();      // A/B switch: 0 = all four tiles of the small branch (round 4-5)
+    static const bool sd_on = slak_env_flag("SLAK_TRI_ROWS_SD", true);      // A/B switch: 0 = all four tiles of the small branch (round 4-5)
     if (p.CPR == 9 && sd_on && H <= 62)
         return bf ? launch_tri_rows_t<bf16_t, 4, 9, true>(p, ws_bytes, st) : launch_tri_rows_t<f16_t, 4, 9, true>(p, ws_bytes, st);
     if (p.CPR == 9) return bf ? launch_tri_rows_t<bf16_t, 4, 9, false>(p, ws_bytes, st) : launch_tri_rows_t<f16_t, 4, 9, false>(p, ws_bytes, st);

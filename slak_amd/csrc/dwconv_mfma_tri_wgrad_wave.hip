@@ -225,10 +225,7 @@ __global__ __launch_bounds__(MF_THREADS, 1) void dwconv_mfma_tri_wgrad_wave_kern
 }
 
 // ------------------------------------------------------------------------------------------------------------
-static bool tri_wave_enabled() {               // SLAK_TRI_WAVE=0: the one-tile planes keep the two-launch weight gradient (A/B testing)
-    static const bool v = [] { const char* e = getenv("SLAK_TRI_WAVE"); return !(e && e[0] == '0'); }();
-    return v;
-}
+static bool tri_wave_enabled() { static const bool v = slak_env_flag("SLAK_TRI_WAVE", true); return v; }   // SLAK_TRI_WAVE=0: the one-tile planes keep the two-launch weight gradient (A/B testing)
 
 static bool fill_tri_wave_params(TriWaveParams& p, int N, int C, int H, int W, int K, int cus) {
     p.N = N; p.C = C; p.H = H; p.W = W; p.K = K; p.padL = K / 2;

@@ -206,14 +206,8 @@ __global__ __launch_bounds__(MF_THREADS, 2) void dwconv_mfma_wgrad_vwave_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------------------
-static bool hwave_enabled() {                  // SLAK_MFMA_HWAVE=0 keeps the stack kernel for the 5 x K weight gradient on these planes (A/B testing)
-    static const bool v = [] { const char* e = getenv("SLAK_MFMA_HWAVE"); return !(e && e[0] == '0'); }();
-    return v;
-}
-static bool vwave_enabled() {                  // SLAK_MFMA_VWAVE=0 keeps the transposing kernel on these planes (A/B testing)
-    static const bool v = [] { const char* e = getenv("SLAK_MFMA_VWAVE"); return !(e && e[0] == '0'); }();
-    return v;
-}
+static bool hwave_enabled() { static const bool v = slak_env_flag("SLAK_MFMA_HWAVE", true); return v; }   // SLAK_MFMA_HWAVE=0 keeps the stack kernel for the 5 x K weight gradient on these planes (A/B testing)
+static bool vwave_enabled() { static const bool v = slak_env_flag("SLAK_MFMA_VWAVE", true); return v; }   // SLAK_MFMA_VWAVE=0 keeps the transposing kernel on these planes (A/B testing)
 static bool fill_vwave_params(WgradWaveParams& p, const ConvDims& d, int resident_wgs) {
     p.N = d.N; p.C = d.C; p.H = d.H; p.W = d.W; p.kh = d.kh; p.kw = d.kw;
     const bool horiz = d.kh == MF_TAPS && d.kw > MF_TAPS;

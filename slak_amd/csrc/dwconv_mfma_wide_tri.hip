@@ -368,10 +368,7 @@ __global__ __launch_bounds__(MF_THREADS, 1) void dwconv_mfma_wide_tri_kernel(con
 }
 
 // ------------------------------------------------------------------------------------------------------------
-static bool wide_tri_enabled() {               // SLAK_WIDE_TRI=0: maps beyond 64 keep the per-branch launches (A/B testing)
-    static const bool v = [] { const char* e = getenv("SLAK_WIDE_TRI"); return !(e && e[0] == '0'); }();
-    return v;
-}
+static bool wide_tri_enabled() { static const bool v = slak_env_flag("SLAK_WIDE_TRI", true); return v; }   // SLAK_WIDE_TRI=0: maps beyond 64 keep the per-branch launches (A/B testing)
 
 static bool fill_wide_tri_params(WideTriParams& p, int N, int C, int H, int W, int K, bool dgrad, int wgs) {
     p.N = N; p.C = C; p.H = H; p.W = W; p.K = K; p.padL = K / 2;

@@ -268,7 +268,7 @@ unsigned* wgrad_arrival_counters(int ngroups) {
     static unsigned* buf[MAXDEV] = {};
     static unsigned next[MAXDEV] = {};
     if (ngroups > MAXG) return nullptr;
-    static const bool force_reduce = [] { const char* e = getenv("SLAK_WGRAD_REDUCE"); return e && e[0] == '1'; }();
+    static const bool force_reduce = slak_env_flag("SLAK_WGRAD_REDUCE", false);
     if (force_reduce) return nullptr;                 // SLAK_WGRAD_REDUCE=1: partials + a separate reduce launch (A/B and debugging)
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAXDEV) return nullptr;

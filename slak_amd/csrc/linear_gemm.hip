@@ -424,7 +424,7 @@ using namespace slak;
 extern "C" {
 
 int slak_linear_gemm_supported(int M, int N, int K, int epilogue) {
-    static const bool on = [] { const char* e = getenv("SLAK_LINEAR_GEMM"); return !(e && e[0] == '0'); }();
+    static const bool on = slak_env_flag("SLAK_LINEAR_GEMM", true);
     Lg2Plan pl;
     return (on && lg2_plan(M, N, K, epilogue, pl)) ? 1 : 0;
 }

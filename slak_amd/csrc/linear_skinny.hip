@@ -827,7 +827,7 @@ int slak_linear_nt(const void* x, const void* wt, const void* bias, void* y, voi
 /* pwconv1 -> GELU -> pwconv2 in ONE pass (see linear_mlp_fwd_k96_kernel): x [M][96], w1 [384][96], b1 [384], w2 [96][384], b2 [96] -> y1, a [M][384],
  * z [M][96], all bf16.  y1 and a: the bits of slak_linear_nt(.., gelu_out); z: those of slak_linear_nt(a, w2, b2) up to fp32 summation order. */
 int slak_linear_mlp_fwd_supported(int M, int C, int C4) {
-    static const bool on = [] { const char* e = getenv("SLAK_LINEAR_MLP_FWD"); return !(e && e[0] == '0'); }();
+    static const bool on = slak_env_flag("SLAK_LINEAR_MLP_FWD", true);
     return (on && M > 0 && C == 96 && C4 == 64 * LM_NP && (long long)M * C4 * 2 < (1LL << 32)) ? 1 : 0;
 }
 int slak_linear_mlp_fwd(const void* x, const void* w1, const void* b1, const void* w2, const void* b2, void* y1, void* a, void* z, int M, int C, int C4,
@@ -851,7 +851,7 @@ int slak_linear_mlp_fwd(const void* x, const void* w1, const void* b1, const voi
  * y1, dy1 [M][N] bf16, dbias [N] fp32.  Round 4: K = 96, N = 384 (stage 1 of SLaK-T/S).  The same dy1 bits as slak_linear_nt followed by
  * slak_gelu_backward_bias; dbias is the same sum of the rounded dy1 in another (fixed) order. */
 int slak_linear_nt_gelu_bwd_supported(int M, int N, int K) {
-    static const bool on = [] { const char* e = getenv("SLAK_LINEAR_GELU_BWD"); return !(e && e[0] == '0'); }();
+    static const bool on = slak_env_flag("SLAK_LINEAR_GELU_BWD", true);
     return (on && M >= 32 && M % 32 == 0 && K == 96 && N == 64 * LG_NP && (long long)M * N * 2 < (1LL << 31)) ? 1 : 0;
 }
 size_t slak_linear_nt_gelu_bwd_workspace_bytes(int M, int N, int K) {
@@ -891,7 +891,7 @@ int slak_pack_w1t_fragments(const void* w1t, void* w1p, int N, int K, void* stre
  * [lane half lhi][8 k] and permuted to [pr][u][j][lhi][l31][8] (slak_pack_w1t_fragments above makes it).  dy1 and dbias: the bits of
  * slak_linear_nt_gelu_bwd; dt: bf16 of the same fp32 sums added in another order than slak_linear_nt's. */
 int slak_linear_nt_gelu_bwd_dt_supported(int M, int N, int K) {
-    static const bool on = [] { const char* e = getenv("SLAK_LINEAR_GELU_BWD_DT"); return !(e && e[0] == '0'); }();
+    static const bool on = slak_env_flag("SLAK_LINEAR_GELU_BWD_DT", true);
     return (on && slak_linear_nt_gelu_bwd_supported(M, N, K)) ? 1 : 0;
 }
 int slak_linear_nt_gelu_bwd_dt(const void* x, const void* wt, const void* y1, const void* w1p, void* dy1, void* dt, float* dbias, int M, int N, int K,

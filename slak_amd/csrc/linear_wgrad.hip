@@ -232,10 +232,7 @@ __global__ __launch_bounds__(256) void linear_wgrad_reduce_few_kernel(const floa
 // ---- host side ---------------------------------------------------------------------------------------------------------------
 struct LwPlan { int w1, w2, nb1, nb2, tiles1, tiles2, S, cps, xcd_map; size_t lds; };
 
-static bool lw_wide_tiles() {                 // SLAK_LINEAR_WGRAD_128=0: the 128 x 64 wave tiles off (A/B: SLaK-B's weight gradients back on the library's split-K GEMM)
-    static const bool v = [] { const char* e = getenv("SLAK_LINEAR_WGRAD_128"); return !(e && e[0] == '0'); }();
-    return v;
-}
+static bool lw_wide_tiles() { static const bool v = slak_env_flag("SLAK_LINEAR_WGRAD_128", true); return v; }   // SLAK_LINEAR_WGRAD_128=0: the 128 x 64 wave tiles off (A/B: SLaK-B's weight gradients back on the library's split-K GEMM)
 
 static bool lw_plan(int M, int N1, int N2, LwPlan& pl) {
     if (M < LW_KC || N1 <= 0 || N2 <= 0) return false;

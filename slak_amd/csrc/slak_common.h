@@ -42,10 +42,8 @@ static inline bool slak_set_max_lds(const void* kernel, size_t lds) {
     return true;
 }
 
-
 // Tuning and experiment knobs (workgroup counts, ring depths, the timing-experiment modes of a kernel) are read from the environment only by DEV builds
-// (SLAK_BUILD_DEFS=-DSLAK_DEV_KNOBS, on top of the per-kernel -DSLAK_*_DEV defines): the shipped library has the measured defaults compiled in.  What stays a
-// plain getenv in the shipped library are the A/B switches that choose between two SHIPPED code paths (SLAK_MFMA_DMA, SLAK_TRI_ROWS, SLAK_LINEAR_GEMM, ...: DESIGN 4).
+// (SLAK_BUILD_DEFS=-DSLAK_DEV_KNOBS, on top of the per-kernel -DSLAK_*_DEV defines): the shipped library has the measured defaults compiled in.
 static inline const char* slak_dev_getenv(const char* name) {
 #ifdef SLAK_DEV_KNOBS
     return getenv(name);
@@ -53,6 +51,12 @@ static inline const char* slak_dev_getenv(const char* name) {
     (void)name;
     return nullptr;
 #endif
+}
+// What the shipped library does read: the A/B switches between two SHIPPED code paths (SLAK_MFMA_DMA, SLAK_TRI_ROWS, SLAK_LINEAR_GEMM, ...: DESIGN 4).  A default-on switch goes
+// off with a leading '0', a default-off one on with a leading '1'.  Call sites keep the answer in a `static const bool`: a thread-safe one-time read (forwards and backwards run on two threads).
+static inline bool slak_env_flag(const char* name, bool default_on) {
+    const char* e = getenv(name);
+    return default_on ? !(e && e[0] == '0') : (e && e[0] == '1');
 }
 
 // ---- element types -------------------------------------------------------------------------
