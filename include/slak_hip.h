@@ -248,7 +248,12 @@ int slak_scale_residual_backward(const float* dout, const void* dout_bf16, float
  *   - columns c >= C of y and of dz are WRITTEN, as +0.0, on every call (the next GEMM reads whole rows);
  *   - columns c >= C of g and z are never used: they may hold anything, NaN included;
  *   - weight, bias, gamma, dweight, dbias, dgamma, dz_colsum are [C].
- * ldc == C (then C % 8 == 0) forwards to the plain entry point: the same bits. */
+ * ldc == C (then C % 8 == 0) forwards to the plain entry point: the same bits.
+ * Kernels: a pitched call runs the small-plane families of the plain entry points (H*W <= 256: a wave per image and group of 24-64 channels, one
+ * pixel per lane on odd planes) exactly where the plain call on C = ldc runs them -- the channel groups tile the pitch, a group's live channel count
+ * is a wave-uniform bound, a group of pad columns only writes its +0 --, plus, for the two LayerNorm ops on odd planes, 64 channels per wave where
+ * ldc / 32 exceeds the 16 waves of a workgroup (C = 998, ldc = 1024).  Then the pixel-pair register-tile kernels (even planes, ldc = 128 / 256 / 512,
+ * ldc - C <= 16), then the LDS-tile kernels.  slak_block_tail_family says which.  The parameter gradients are summed in a fixed order in every family. */
 int slak_ln_nchw_to_nhwc_forward_ld(const void* x_bf16, const float* weight, const float* bias, void* y_bf16, float* mean, float* rstd,
                                     int N, int C, int P, float eps, void* stream, int ldc);
 int slak_ln_nchw_to_nhwc_backward_ld(const void* g_bf16, const void* x_bf16, const float* weight, const float* mean, const float* rstd,
@@ -259,6 +264,14 @@ int slak_scale_residual_forward_ld(const void* shortcut, int shortcut_dtype, con
 int slak_scale_residual_backward_ld(const float* dout, const void* dout_bf16, float* dout_sum, const void* z_bf16, const float* gamma,
                                     const float* sample_scale, void* dz_bf16, float* dgamma, float* dz_colsum, int N, int C, int P,
                                     void* workspace, size_t workspace_bytes, void* stream, int ldc);
+
+/* Which kernel family the block-tail entry points run for `op` on (N, C, P) with NHWC rows of ldc elements; ldc == C asks for the plain entry
+ * point's choice.  Pure host code, callable without a device; the eight entry points choose their kernel through this very function, so the answer
+ * IS the launch.  NONE: the entry point would not launch (invalid or unsupported arguments; shortcut_dtype matters to SLAK_TAIL_SR_FWD only).
+ * TILE: LDS-tile kernels; REG: pixel-pair register-tile kernels; CHAN / CHAN1: the small-plane families, even / odd H*W. */
+enum { SLAK_TAIL_LN_FWD = 0, SLAK_TAIL_LN_BWD = 1, SLAK_TAIL_SR_FWD = 2, SLAK_TAIL_SR_BWD = 3 };
+enum { SLAK_TAIL_FAMILY_NONE = 0, SLAK_TAIL_FAMILY_TILE = 1, SLAK_TAIL_FAMILY_REG = 2, SLAK_TAIL_FAMILY_CHAN = 3, SLAK_TAIL_FAMILY_CHAN1 = 4 };
+int slak_block_tail_family(int op, int shortcut_dtype, int N, int C, int P, int ldc);
 
 /* Downsample layers (models/SLaK.py:285-311: LayerNorm(C, data_format="channels_first") -> Conv2d(C, C', kernel_size=2, stride=2)).  The
  * kernel/stride-2 convolution is a GEMM on non-overlapping 2x2 patches; slak_ln_patch_forward normalises the fp32 NCHW input over C and

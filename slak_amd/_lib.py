@@ -155,8 +155,13 @@ SIGNATURES = {
     "slak_ln_nchw_to_nhwc_backward_ld": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp, _i]),
     "slak_scale_residual_forward_ld": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i]),
     "slak_scale_residual_backward_ld": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp, _i]),
+    "slak_block_tail_family": (_i, [_i, _i, _i, _i, _i, _i]),      # (op, shortcut_dtype, N, C, P, ldc) -> TAIL_FAMILY_*; host only
     "slak_pad_cast_bf16_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
 }
+# slak_block_tail_family: ops and answers (include/slak_hip.h)
+TAIL_LN_FWD, TAIL_LN_BWD, TAIL_SR_FWD, TAIL_SR_BWD = 0, 1, 2, 3
+TAIL_FAMILY_NONE, TAIL_FAMILY_TILE, TAIL_FAMILY_REG, TAIL_FAMILY_CHAN, TAIL_FAMILY_CHAN1 = 0, 1, 2, 3, 4
+TAIL_FAMILY_NAMES = ("none", "tile", "reg", "chan", "chan1")
 
 
 def lib():

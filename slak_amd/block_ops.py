@@ -24,6 +24,7 @@ def _chk(t, name, dtype=None):
 
 pad_even_widths = os.environ.get("SLAK_PAD_EVEN", "0") == "1"     # also pad the even widths that are no multiple of 32 (124 -> 128, 998 -> 1024): aligned GEMM rows at width 1.3
 pitched_block_hits = 0                                             # block tails / whole blocks that ran on pitched NHWC tensors so far (tests, tools/time_width.py)
+pitched_runner_hits = 0                                            # ... of them the whole blocks that the C++ runner issued (the others: the Python sequence)
 
 
 def nhwc_pitch(C):
@@ -1601,22 +1602,33 @@ class _BlockFn(torch.autograd.Function):
         if ldc is None:
             raise _lib.SlakHipError("fused_block: no fused tail for C = %d (C <= 1024)" % C)
         ctx.pitch = (C, ldc) if ldc != C else None
-        R = _runner() if ldc == C else None                           # the C++ runner issues the plain entry points only: a pitched block (odd C, or an even
-        # width under pad_even_widths) takes the Python sequence below
+        global pitched_block_hits, pitched_runner_hits
+        padded = None                                                 # (W1p, b1p, W2p, b2p, W1p^T, W2p^T) of a pitched block
+        R = _runner()                                                 # a pitched block (odd C, or an even width under pad_even_widths) hands the runner the pitch and
+        # the zero-padded operands; where it declines (an empty list) the Python sequence below runs
         if (R is not None and bns[0].momentum is not None and x.is_contiguous()
                 and all(bn.track_running_stats and bn.num_batches_tracked is not None for bn in bns)):
-            w1b, w2b = lowp_param(w1), lowp_param(w2)
+            if ctx.pitch is not None:
+                padded = _pitched_operands(w1, bb1, w2, bb2, ldc)
+                w1b, bb1b, w2b, bb2b, w1pt, w2pt = padded
+            else:
+                w1b, bb1b, w2b, bb2b = lowp_param(w1), lowp_param(bb1), lowp_param(w2), lowp_param(bb2)
             group = _bn3_group(bns[0])                                # SyncBatchNorm: the runner calls back for the two statistics exchanges
             exchange = _runner_exchange(group)
             res = R.block_forward(x, x_lowp, wv, wh, ws, [g1, g2, g3], [b1, b2, b3], [bn.running_mean for bn in bns], [bn.running_var for bn in bns],
-                                  float(bns[0].eps), float(bns[0].momentum), True, lnw, lnb, float(eps), w1b, lowp_param(bb1), w2b, lowp_param(bb2),
-                                  gamma, sample_scale, bool(emit), exchange)
+                                  float(bns[0].eps), float(bns[0].momentum), True, lnw, lnb, float(eps), w1b, bb1b, w2b, bb2b,
+                                  gamma, sample_scale, bool(emit), exchange, int(ldc))
             if res:                                                   # (empty: the shape has no one-launch path -- the Python sequence knows the fallbacks)
                 out, out16, x16, yv, yh, ys, bnstats, s, t, mean, rstd, y1m, a, z, count_dev = res
                 pool = getattr(bns[0], "_slak_ctr_pool", None)
                 if not (pool is not None and pool.covers(bns) and pool.bump_once()):
                     torch._foreach_add_([bn.num_batches_tracked for bn in bns], 1)
-                wts = (lowp_param_t(w1), lowp_param_t(w2)) if cache_lowp_weights else (None, None)
+                if ctx.pitch is not None:
+                    wts = (w1pt, w2pt)
+                    pitched_block_hits += 1
+                    pitched_runner_hits += 1
+                else:
+                    wts = (lowp_param_t(w1), lowp_param_t(w2)) if cache_lowp_weights else (None, None)
                 ctx.save_for_backward(x16, wv, wh, ws, yv, yh, ys, g1, g2, g3, bnstats, s, lnw, mean, rstd, t, w1b, y1m, a, w2b, z, gamma, sample_scale, *wts)
                 ctx.misc = (True, group, float(x.shape[0] * x.shape[2] * x.shape[3]), count_dev, x.dtype, x_lowp is not None)
                 ctx.runner = True
@@ -1631,8 +1643,7 @@ class _BlockFn(torch.autograd.Function):
         s, bnstats, count, count_dev = _bn3_forward_impl(yv, yh, ys, [g1, g2, g3], [b1, b2, b3], bns, group, pre)
         t, mean, rstd = _ln_fwd_impl(s, lnw, lnb, eps, ldc)
         if ctx.pitch is not None:
-            global pitched_block_hits
-            w1p, b1p, w2p, b2p, w1pt, w2pt = _pitched_operands(w1, bb1, w2, bb2, ldc)
+            w1p, b1p, w2p, b2p, w1pt, w2pt = padded if padded is not None else _pitched_operands(w1, bb1, w2, bb2, ldc)
             tab = {id(w1): w1p, id(bb1): b1p, id(w2): w2p, id(bb2): b2p}
             z, saved = _mlp_fwd(t, w1, bb1, w2, bb2, cast=lambda p: tab[id(p)])
             pitched_block_hits += 1
@@ -1662,7 +1673,7 @@ class _BlockFn(torch.autograd.Function):
                 w1p = w1_fragments(w1t if w1t is not None else w1b.t().contiguous())
             res = _runner_mod.block_backward(
                 x16, wv, wh, ws, yv, yh, ys, [g1, g2, g3], bnstats, s, lnw, mean, rstd, t, w1b, y1m, a, w2b, z, gamma, sample_scale, dout, dout16,
-                xdtype == torch.bfloat16, had_lowp, count_dev, exchange, _runner_trace, w1t, w2t, w1p, _grad_destinations(ctx.params))
+                xdtype == torch.bfloat16, had_lowp, count_dev, exchange, _runner_trace, w1t, w2t, w1p, _grad_destinations(ctx.params), int(w1b.shape[1]))
             return (*res, None, None)                                 # dx, dx_lowp, then the sixteen parameter gradients in forward()'s order
         saved = (t, w1b, y1m, a, w2b)
         dshortcut, dz, dgamma, dzc = _scale_residual_bwd(z, gamma, sample_scale, xdtype, dout, dout16)

@@ -1265,14 +1265,33 @@ static int tail_args_ok(int N, int C, int P) {
     return SLAK_OK;
 }
 
+// ---- pitched NHWC side: any C <= 1024, rows of ldc >= C elements (ldc % 8 == 0, <= 1024); ldc == C is the plain entry point, bit for bit
+static int tail_args_ok_ld(int N, int C, int P, int ldc) {
+    if (N <= 0 || C <= 0 || P <= 0) return SLAK_ERR_INVALID_ARG;
+    if (C > 1024 || ldc < C || (ldc & 7) || ldc > 1024) return SLAK_ERR_UNSUPPORTED;
+    if ((long long)N * ldc * P >= (1LL << 31)) return SLAK_ERR_UNSUPPORTED;
+    return SLAK_OK;
+}
+
+// The family an entry point runs: the eight of them branch on this function's answer (a family of block_tail_reg.hip: its launcher, which asks
+// the same rt_tail_choice; TILE: the kernels of this file), so the query cannot disagree with the launch.
+int slak_block_tail_family(int op, int shortcut_dtype, int N, int C, int P, int ldc) {
+    if (op < SLAK_TAIL_LN_FWD || op > SLAK_TAIL_SR_BWD) return SLAK_TAIL_FAMILY_NONE;
+    if (ldc == C ? tail_args_ok(N, C, P) : tail_args_ok_ld(N, C, P, ldc)) return SLAK_TAIL_FAMILY_NONE;
+    if (op == SLAK_TAIL_SR_FWD && shortcut_dtype != SLAK_F32 && shortcut_dtype != SLAK_BF16) return SLAK_TAIL_FAMILY_NONE;
+    if (tail_use_reg()) {                               // register-tile and small-plane kernels (block_tail_reg.hip) where an instantiation exists
+        const RtChoice ch = rt_tail_choice(op, shortcut_dtype, N, C, ldc, P);
+        if (ch.family != SLAK_TAIL_FAMILY_NONE) return ch.family;
+    }
+    return SLAK_TAIL_FAMILY_TILE;
+}
+
 int slak_ln_nchw_to_nhwc_forward(const void* x, const float* weight, const float* bias, void* y, float* mean, float* rstd,
                                  int N, int C, int P, float eps, void* stream) {
     if (!x || !weight || !bias || !y || !mean || !rstd) return SLAK_ERR_INVALID_ARG;
     int rc = tail_args_ok(N, C, P); if (rc) return rc;
-    if (tail_use_reg()) {                               // register-tile kernel (block_tail_reg.hip) where an instantiation exists
-        rc = launch_ln_nchw_to_nhwc_fwd_reg(x, weight, bias, y, mean, rstd, N, C, P, eps, (hipStream_t)stream);
-        if (rc != SLAK_ERR_UNSUPPORTED) return rc;
-    }
+    if (slak_block_tail_family(SLAK_TAIL_LN_FWD, 0, N, C, P, C) != SLAK_TAIL_FAMILY_TILE)
+        return launch_ln_nchw_to_nhwc_fwd_reg(x, weight, bias, y, mean, rstd, N, C, P, eps, (hipStream_t)stream);
     if (C <= 256) {
         const TailDims d = make_dims_pix(N, C, P);
         const size_t lds = (((size_t)C * (d.TP + 2) * 2 + 15) & ~(size_t)15) + (size_t)(BT_THREADS / d.TP) * d.TP * 4 + 2 * d.TP * 4;
@@ -1297,11 +1316,11 @@ int slak_ln_nchw_to_nhwc_backward(const void* g, const void* x, const float* wei
     if (!g || !x || !weight || !mean || !rstd || !dx || !dweight || !dbias) return SLAK_ERR_INVALID_ARG;
     int rc = tail_args_ok(N, C, P); if (rc) return rc;
     if (!workspace || workspace_bytes < slak_block_tail_workspace_bytes(N, C, P)) return SLAK_ERR_WORKSPACE;
-    if (tail_use_reg()) {
+    if (slak_block_tail_family(SLAK_TAIL_LN_BWD, 0, N, C, P, C) != SLAK_TAIL_FAMILY_TILE) {
         int rows = 0; float* part = (float*)workspace;
         rc = launch_ln_nchw_to_nhwc_bwd_reg(g, x, weight, mean, rstd, dx, part, &rows, N, C, P, (hipStream_t)stream);
         if (rc == SLAK_OK) return reduce_partials(part, part + (size_t)rows * 2 * C, dweight, dbias, C, rows, 2 * C, (hipStream_t)stream);
-        if (rc != SLAK_ERR_UNSUPPORTED) return rc;
+        return rc;
     }
     if (C <= 256) {
         const TailDims d = make_dims_pix(N, C, P);
@@ -1441,9 +1460,11 @@ int slak_scale_residual_forward(const void* shortcut, int shortcut_dtype, const 
                                 float* out, void* out_bf16, int N, int C, int P, void* stream) {
     if (!shortcut || !z || !gamma || !out) return SLAK_ERR_INVALID_ARG;
     int rc = tail_args_ok(N, C, P); if (rc) return rc;
-    if (tail_use_reg()) {
-        rc = launch_scale_residual_fwd_reg(shortcut, shortcut_dtype, z, gamma, sample_scale, out, out_bf16, N, C, P, (hipStream_t)stream);
-        if (rc != SLAK_ERR_UNSUPPORTED) return rc;
+    {
+        const int fam = slak_block_tail_family(SLAK_TAIL_SR_FWD, shortcut_dtype, N, C, P, C);
+        if (fam == SLAK_TAIL_FAMILY_NONE) return SLAK_ERR_UNSUPPORTED;             // (the shortcut's dtype)
+        if (fam != SLAK_TAIL_FAMILY_TILE)
+            return launch_scale_residual_fwd_reg(shortcut, shortcut_dtype, z, gamma, sample_scale, out, out_bf16, N, C, P, (hipStream_t)stream);
     }
     if (C <= 256) {
         const TailDims d = make_dims_pix(N, C, P);
@@ -1485,11 +1506,11 @@ int slak_scale_residual_backward(const float* dout, const void* dout_bf16, float
     if (!dout || !z || !gamma || !dz || !dgamma || !dz_colsum || (dout_bf16 && !dout_sum)) return SLAK_ERR_INVALID_ARG;
     int rc = tail_args_ok(N, C, P); if (rc) return rc;
     if (!workspace || workspace_bytes < slak_block_tail_workspace_bytes(N, C, P)) return SLAK_ERR_WORKSPACE;
-    if (tail_use_reg()) {
+    if (slak_block_tail_family(SLAK_TAIL_SR_BWD, 0, N, C, P, C) != SLAK_TAIL_FAMILY_TILE) {
         int rows = 0; float* part = (float*)workspace;
         rc = launch_scale_residual_bwd_reg(dout, dout_bf16, dout_sum, z, gamma, sample_scale, dz, part, &rows, N, C, P, (hipStream_t)stream);
         if (rc == SLAK_OK) return reduce_partials(part, part + (size_t)rows * 2 * C, dgamma, dz_colsum, C, rows, 2 * C, (hipStream_t)stream);
-        if (rc != SLAK_ERR_UNSUPPORTED) return rc;
+        return rc;
     }
     if (C <= 256) {
         const TailDims d = make_dims_pix(N, C, P);
@@ -1513,23 +1534,14 @@ int slak_scale_residual_backward(const float* dout, const void* dout_bf16, float
     return reduce_partials(part, part + (size_t)grid * 2 * C, dgamma, dz_colsum, C, grid, 2 * C, (hipStream_t)stream);
 }
 
-// ---- pitched NHWC side: any C <= 1024, rows of ldc >= C elements (ldc % 8 == 0, <= 1024); ldc == C is the plain entry point, bit for bit
-static int tail_args_ok_ld(int N, int C, int P, int ldc) {
-    if (N <= 0 || C <= 0 || P <= 0) return SLAK_ERR_INVALID_ARG;
-    if (C > 1024 || ldc < C || (ldc & 7) || ldc > 1024) return SLAK_ERR_UNSUPPORTED;
-    if ((long long)N * ldc * P >= (1LL << 31)) return SLAK_ERR_UNSUPPORTED;
-    return SLAK_OK;
-}
-
+// ---- the pitched entry points (tail_args_ok_ld above)
 int slak_ln_nchw_to_nhwc_forward_ld(const void* x, const float* weight, const float* bias, void* y, float* mean, float* rstd,
                                     int N, int C, int P, float eps, void* stream, int ldc) {
     if (!x || !weight || !bias || !y || !mean || !rstd) return SLAK_ERR_INVALID_ARG;
     int rc = tail_args_ok_ld(N, C, P, ldc); if (rc) return rc;
     if (ldc == C) return slak_ln_nchw_to_nhwc_forward(x, weight, bias, y, mean, rstd, N, C, P, eps, stream);
-    if (tail_use_reg()) {                               // register-tile kernel on the instantiation whose channel count is the pitch
-        rc = launch_ln_nchw_to_nhwc_fwd_reg_ld(x, weight, bias, y, mean, rstd, N, C, ldc, P, eps, (hipStream_t)stream);
-        if (rc != SLAK_ERR_UNSUPPORTED) return rc;
-    }
+    if (slak_block_tail_family(SLAK_TAIL_LN_FWD, 0, N, C, P, ldc) != SLAK_TAIL_FAMILY_TILE)       // small-plane family, or the register-tile kernel whose channel count is the pitch
+        return launch_ln_nchw_to_nhwc_fwd_reg_ld(x, weight, bias, y, mean, rstd, N, C, ldc, P, eps, (hipStream_t)stream);
     const TailDims d = make_dims(N, C, P, 2);
     const size_t lds = (size_t)C * (d.TP + 2) * 2 + 16;
     if (set_lds((const void*)ln_nchw_to_nhwc_fwd_ld_kernel, lds)) return SLAK_ERR_LAUNCH;
@@ -1546,11 +1558,11 @@ int slak_ln_nchw_to_nhwc_backward_ld(const void* g, const void* x, const float* 
     int rc = tail_args_ok_ld(N, C, P, ldc); if (rc) return rc;
     if (ldc == C) return slak_ln_nchw_to_nhwc_backward(g, x, weight, mean, rstd, dx, dweight, dbias, N, C, P, workspace, workspace_bytes, stream);
     if (!workspace || workspace_bytes < slak_block_tail_workspace_bytes(N, ldc, P)) return SLAK_ERR_WORKSPACE;
-    if (tail_use_reg()) {
+    if (slak_block_tail_family(SLAK_TAIL_LN_BWD, 0, N, C, P, ldc) != SLAK_TAIL_FAMILY_TILE) {
         int rows = 0;
         rc = launch_ln_nchw_to_nhwc_bwd_reg_ld(g, x, weight, mean, rstd, dx, (float*)workspace, &rows, N, C, ldc, P, (hipStream_t)stream);
         if (rc == SLAK_OK) return reduce_partials_ld((const float*)workspace, dweight, dbias, ldc, C, rows, (hipStream_t)stream);
-        if (rc != SLAK_ERR_UNSUPPORTED) return rc;
+        return rc;
     }
     const TailDims d = make_dims(N, C, P, 2);
     const size_t lds = (((size_t)C * (d.TP + 2) * 2 + 15) & ~(size_t)15) + (size_t)4 * 2 * C * 4;
@@ -1569,10 +1581,8 @@ int slak_scale_residual_forward_ld(const void* shortcut, int shortcut_dtype, con
     int rc = tail_args_ok_ld(N, C, P, ldc); if (rc) return rc;
     if (ldc == C) return slak_scale_residual_forward(shortcut, shortcut_dtype, z, gamma, sample_scale, out, out_bf16, N, C, P, stream);
     if (shortcut_dtype != SLAK_F32 && shortcut_dtype != SLAK_BF16) return SLAK_ERR_UNSUPPORTED;
-    if (tail_use_reg()) {
-        rc = launch_scale_residual_fwd_reg_ld(shortcut, shortcut_dtype, z, gamma, sample_scale, out, out_bf16, N, C, ldc, P, (hipStream_t)stream);
-        if (rc != SLAK_ERR_UNSUPPORTED) return rc;
-    }
+    if (slak_block_tail_family(SLAK_TAIL_SR_FWD, shortcut_dtype, N, C, P, ldc) != SLAK_TAIL_FAMILY_TILE)
+        return launch_scale_residual_fwd_reg_ld(shortcut, shortcut_dtype, z, gamma, sample_scale, out, out_bf16, N, C, ldc, P, (hipStream_t)stream);
     const int zp = 2 * ((C + 1) / 2) + 2;                           // the NHWC tile is [TP][zp]: same byte count as [C][TP+2] up to the padding
     TailDims d = make_dims(N, C, P, 2);
     while (d.TP > 16 && (size_t)d.TP * zp * 2 > 50 * 1024) { d.TP /= 2; d.tiles_per_image = (P + d.TP - 1) / d.TP; d.ntiles = N * d.tiles_per_image; }
@@ -1599,11 +1609,11 @@ int slak_scale_residual_backward_ld(const float* dout, const void* dout_bf16, fl
     if (ldc == C) return slak_scale_residual_backward(dout, dout_bf16, dout_sum, z, gamma, sample_scale, dz, dgamma, dz_colsum, N, C, P,
                                                       workspace, workspace_bytes, stream);
     if (!workspace || workspace_bytes < slak_block_tail_workspace_bytes(N, ldc, P)) return SLAK_ERR_WORKSPACE;
-    if (tail_use_reg()) {
+    if (slak_block_tail_family(SLAK_TAIL_SR_BWD, 0, N, C, P, ldc) != SLAK_TAIL_FAMILY_TILE) {
         int rows = 0;
         rc = launch_scale_residual_bwd_reg_ld(dout, dout_bf16, dout_sum, z, gamma, sample_scale, dz, (float*)workspace, &rows, N, C, ldc, P, (hipStream_t)stream);
         if (rc == SLAK_OK) return reduce_partials_ld((const float*)workspace, dgamma, dz_colsum, ldc, C, rows, (hipStream_t)stream);
-        if (rc != SLAK_ERR_UNSUPPORTED) return rc;
+        return rc;
     }
     const TailDims d = make_dims(N, C, P, 4);
     size_t lds = (size_t)C * (d.TP + 1) * 4 + 16;

@@ -414,11 +414,33 @@ __global__ __launch_bounds__(256, 2) void scale_residual_fwd_reg_kernel(const Ts
 // 3.2 TB/s against 5.7 on the 56 x 56 stage).  Here a wave takes CW channels of ONE image over 64 pixel pairs: a channel row is read and
 // written as one 512-byte run (256 for the bf16 copy), and the lane fetches the CW channels of its two pixels of z as 16-byte pieces
 // straight into registers (no LDS tile, no barrier).  Same arithmetic, same rounding.
-template <int CW>
+// LD (the pitched entry points, slak_*_ld) in this family and in the one-pixel-per-lane family below: C is the PITCH -- the NHWC rows and the channel groups
+// tile it -- and the NCHW tensors and the per-channel parameters have Cl <= C rows.  A wave's group holds `live` = clamp(Cl - cg * CW, 0, CW)
+// channels, possibly none: a wave-uniform number, so it bounds the channel loops as a SCALAR (uniform branches and scalar selects, no per-lane
+// select and no register for it).  Rows c >= live are neither read nor written on the NCHW side and no parameter is read for them; what the
+// 16-byte pieces of g / z carry in their pad columns is cleared by rt_mask_live before any arithmetic (never multiplied by a zero), and the
+// pad columns of y / dz come out as +0 because every factor of theirs is an exact zero.  In a guarded loop the loads stand alone and their uses follow
+// behind ALL of them: a load used inside its own guarded block is waited for there, row after row.  The plain instantiations compile to the code they were.
+template <int CW> __device__ __forceinline__ int rt_live(int Cl, int cg) { const int r = Cl - cg * CW; return r < 0 ? 0 : (r > CW ? CW : r); }
+template <int CW> __device__ __forceinline__ void rt_mask_live(rt_u32x4 (&a)[CW / 8], int live) {
+    if (live >= CW) return;
+#pragma unroll
+    for (int d = 0; d < CW / 2; ++d) {                            // dword d = channels 2d, 2d + 1
+        const unsigned m = 2 * d + 1 < live ? 0xffffffffu : (2 * d < live ? 0x0000ffffu : 0u);
+        a[d >> 2][d & 3] &= m;
+    }
+}
+// LD, the kernels that use a group's parameters many times: they sit in ONE register, lane c holding parameter c (zero behind the live ones, never
+// fetched there), and are read with v_readlane -- a guarded scalar load per use (clamped index, select, its own wait) made these kernels 4-20 us slower.
+template <int CW> __device__ __forceinline__ float rt_lane_par(const float* __restrict__ p, int base, int lane, int Cl) {
+    return (lane < CW && base + lane < Cl) ? p[base + lane] : 0.f;
+}
+__device__ __forceinline__ float rt_rl(float v, int c) { return __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(v), c)); }
+template <int CW, bool LD = false>
 __global__ __launch_bounds__(256) void scale_residual_fwd_chan_kernel(const float* __restrict__ sc, const uint16_t* __restrict__ z,
                                                                       const float* __restrict__ gamma, const float* __restrict__ scale,
                                                                       float* __restrict__ out, uint16_t* __restrict__ out16,
-                                                                      int C, int P, int rounds, int nunits) {
+                                                                      int C, int P, int rounds, int nunits, int Cl) {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int unit = blockIdx.x * 4 + wave;                       // (image, channel group, round of 64 pixel pairs)
     if (unit >= nunits) return;
@@ -426,22 +448,29 @@ __global__ __launch_bounds__(256) void scale_residual_fwd_chan_kernel(const floa
     const int rd = unit % rounds, t = unit / rounds, cg = t % groups, n = t / groups;
     const int pair = rd * 64 + lane;
     if (2 * pair >= P) return;                                    // (no barrier in the kernel: lanes may leave)
+    const int Cq = LD ? Cl : C, live = LD ? rt_live<CW>(Cl, cg) : CW;   // channel rows of the NCHW tensors; of this group
+    if (LD && live == 0) return;                                  // a group of pad columns: nothing on the NCHW side
     const float sn = scale ? scale[n] : 1.0f;
     const uint16_t* zp = z + ((size_t)n * P + 2 * pair) * C + cg * CW;
     rt_u32x4 za[CW / 8], zb[CW / 8];
 #pragma unroll
     for (int j = 0; j < CW / 8; ++j) { za[j] = *(const rt_u32x4*)(zp + j * 8); zb[j] = *(const rt_u32x4*)(zp + C + j * 8); }
-    const size_t row0 = ((size_t)n * C + cg * CW) * P + 2 * pair;
+    const size_t row0 = ((size_t)n * Cq + cg * CW) * P + 2 * pair;
     float sx[CW], sy[CW];
 #pragma unroll
-    for (int c = 0; c < CW; ++c) { const float2 v = *(const float2*)(sc + row0 + (size_t)c * P); sx[c] = v.x; sy[c] = v.y; }
+    for (int c = 0; c < CW; ++c) {
+        if (c < live) { const float2 v = *(const float2*)(sc + row0 + (size_t)c * P); sx[c] = v.x; sy[c] = v.y; }
+        else { sx[c] = 0.f; sy[c] = 0.f; }
+    }
     const float* gp = gamma + cg * CW;
 #pragma unroll
     for (int c = 0; c < CW; ++c) {
+        if (c < live) {                                           // (LD: the rows behind it do not exist, nor their gamma)
         const float gm = gp[c] * sn;                              // (wave-uniform: a scalar load)
         const float ox = sx[c] + gm * RT_CH(za[c >> 3], c & 7), oy = sy[c] + gm * RT_CH(zb[c >> 3], c & 7);
         *(float2*)(out + row0 + (size_t)c * P) = float2{ox, oy};
         if (out16) *(unsigned*)(out16 + row0 + (size_t)c * P) = rt_pack2(ox, oy);
+        }
     }
 }
 
@@ -537,12 +566,12 @@ __global__ __launch_bounds__(256, 2) void scale_residual_bwd_reg_kernel(const fl
 // fp32 gradient rows (10 of the 14 bytes per element with the bf16 second stream and the summed output) move as 512-byte runs, z and dz
 // as 16-byte pieces from / to registers.  The wave holds ALL of its channels' pixels of the round, so the per-channel sums are one fold
 // over the wave (rt_fold4 + four shuffles) and land in row (image, round) of the partial matrix: columns of the wave's channels only.
-template <int CW>
+template <int CW, bool LD = false>
 __global__ __launch_bounds__(256) void scale_residual_bwd_chan_kernel(const float* __restrict__ dout, const uint16_t* __restrict__ dout16,
                                                                       float* __restrict__ dsum, const uint16_t* __restrict__ z,
                                                                       const float* __restrict__ gamma, const float* __restrict__ scale,
                                                                       uint16_t* __restrict__ dz, float* __restrict__ part,
-                                                                      int C, int P, int rounds, int nunits) {
+                                                                      int C, int P, int rounds, int nunits, int Cl) {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int unit = blockIdx.x * 4 + wave;                       // (image, channel group, round of 64 pixel pairs)
     if (unit >= nunits) return;                                   // (no workgroup barrier in the kernel)
@@ -550,22 +579,40 @@ __global__ __launch_bounds__(256) void scale_residual_bwd_chan_kernel(const floa
     const int rd = unit % rounds, t = unit / rounds, cg = t % groups, n = t / groups;
     const int pair = rd * 64 + lane;
     const bool valid = 2 * pair < P;
+    const int Cq = LD ? Cl : C, live = LD ? rt_live<CW>(Cl, cg) : CW;   // channel rows of the NCHW tensors; of this group (a group of pad columns still writes its dz as +0)
+    const float gv = LD ? rt_lane_par<CW>(gamma, cg * CW, lane, Cl) : 0.f;
+    const float* gp = gamma + cg * CW;
     const float sn = scale ? scale[n] : 1.0f;
     const size_t zoff = ((size_t)n * P + 2 * pair) * C + cg * CW;
-    const size_t row0 = ((size_t)n * C + cg * CW) * P + 2 * pair;
+    const size_t row0 = ((size_t)n * Cq + cg * CW) * P + 2 * pair;
     rt_u32x4 za[CW / 8], zb[CW / 8];
     float vx[CW], vy[CW];
-    if (valid) {
+    if (valid && live > 0) {
 #pragma unroll
         for (int j = 0; j < CW / 8; ++j) { za[j] = *(const rt_u32x4*)(z + zoff + j * 8); zb[j] = *(const rt_u32x4*)(z + zoff + C + j * 8); }
+        if constexpr (LD) { rt_mask_live<CW>(za, live); rt_mask_live<CW>(zb, live); }       // the pad columns of z: cleared, not multiplied away
 #pragma unroll
-        for (int c = 0; c < CW; ++c) { const float2 v = *(const float2*)(dout + row0 + (size_t)c * P); vx[c] = v.x; vy[c] = v.y; }
+        for (int c = 0; c < CW; ++c) {
+            if (c < live) { const float2 v = *(const float2*)(dout + row0 + (size_t)c * P); vx[c] = v.x; vy[c] = v.y; }
+            else { vx[c] = 0.f; vy[c] = 0.f; }
+        }
         if (dout16) {
+            if constexpr (LD) {                                    // loads first, uses behind them: a load used inside its own guarded block is waited for there, row after row
+                unsigned h[CW];
+#pragma unroll
+                for (int c = 0; c < CW; ++c) h[c] = c < live ? *(const unsigned*)(dout16 + row0 + (size_t)c * P) : 0u;
+#pragma unroll
+                for (int c = 0; c < CW; ++c) {
+                    vx[c] += rt_lo(h[c]); vy[c] += rt_hi(h[c]);
+                    if (c < live) *(float2*)(dsum + row0 + (size_t)c * P) = float2{vx[c], vy[c]};
+                }
+            } else {
 #pragma unroll
             for (int c = 0; c < CW; ++c) {
                 const unsigned h = *(const unsigned*)(dout16 + row0 + (size_t)c * P);
                 vx[c] += rt_lo(h); vy[c] += rt_hi(h);
                 *(float2*)(dsum + row0 + (size_t)c * P) = float2{vx[c], vy[c]};
+            }
             }
         }
     } else {                                                       // lanes past the image contribute zeros to the sums
@@ -574,7 +621,6 @@ __global__ __launch_bounds__(256) void scale_residual_bwd_chan_kernel(const floa
 #pragma unroll
         for (int c = 0; c < CW; ++c) { vx[c] = 0.f; vy[c] = 0.f; }
     }
-    const float* gp = gamma + cg * CW;
     float accg[CW / 4], accs[CW / 4];
 #pragma unroll
     for (int j = 0; j < CW / 8; ++j) {
@@ -589,7 +635,7 @@ __global__ __launch_bounds__(256) void scale_residual_bwd_chan_kernel(const floa
         rt_u32x4 oa, ob;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const float g0 = gp[j * 8 + 2 * k], g1 = gp[j * 8 + 2 * k + 1];       // (wave-uniform: scalar loads)
+            const float g0 = LD ? rt_rl(gv, j * 8 + 2 * k) : gp[j * 8 + 2 * k], g1 = LD ? rt_rl(gv, j * 8 + 2 * k + 1) : gp[j * 8 + 2 * k + 1];       // (wave-uniform: scalar loads)
             oa[k] = rt_pack2(g0 * d0[2 * k], g1 * d0[2 * k + 1]);
             ob[k] = rt_pack2(g0 * d1[2 * k], g1 * d1[2 * k + 1]);
         }
@@ -605,7 +651,8 @@ __global__ __launch_bounds__(256) void scale_residual_bwd_chan_kernel(const floa
         float a = accg[m], b = accs[m];
 #pragma unroll
         for (int k = 1; k < 16; k <<= 1) { a += __shfl_xor(a, k, 64); b += __shfl_xor(b, k, 64); }
-        if ((lane & 15) == 0) { const int c = 4 * m + cofs; prow[c] = a; prow[C + c] = b * gp[c]; }
+        const float gc = LD ? __shfl(gv, 4 * m + cofs, 64) : 0.f;
+        if ((lane & 15) == 0) { const int c = 4 * m + cofs; prow[c] = a; prow[C + c] = b * (LD ? gc : gp[c]); }
     }
 }
 
@@ -613,24 +660,29 @@ __global__ __launch_bounds__(256) void scale_residual_bwd_chan_kernel(const floa
 // (<= 8 waves), so the bf16 NCHW rows move as 256-byte runs; the per-pixel sums over C are the sum of the waves' partials through LDS (one
 // workgroup barrier), the per-channel sums one fold over the wave.  (The forward in this mapping measured slower inside a training step than
 // the pixel-tile kernel, 16.7 vs 14.9 us on 384 x 14 x 14 -- its input was just written and is cache resident -- and was dropped.)
-template <int CW>
+// LD: a wave whose group is all pad columns loads nothing, adds zeros to the workgroup's sums and still meets the barrier.
+template <int CW, bool LD = false>
 __global__ __launch_bounds__(512) void ln_nchw_to_nhwc_bwd_chan_kernel(const uint16_t* __restrict__ gy, const uint16_t* __restrict__ x, const float* __restrict__ w,
                                                                        const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                                       uint16_t* __restrict__ dx, float* __restrict__ part, int C, int P, int rounds) {
+                                                                       uint16_t* __restrict__ dx, float* __restrict__ part, int C, int P, int rounds, int Cl) {
     __shared__ float4 red[8][64];
     const int lane = threadIdx.x & 63, cg = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), nw = (int)(blockDim.x >> 6);
     const int rd = blockIdx.x % rounds, n = blockIdx.x / rounds;
     const int pair = rd * 64 + lane;
     const bool valid = 2 * pair < P;
-    const size_t row0 = ((size_t)n * C + cg * CW) * P + 2 * pair, goff = ((size_t)n * P + 2 * pair) * C + cg * CW;
+    const int Cq = LD ? Cl : C, live = LD ? rt_live<CW>(Cl, cg) : CW;   // channel rows of the NCHW tensors; of this group
+    const float wv = LD ? rt_lane_par<CW>(w, cg * CW, lane, Cl) : 0.f;
+    const float* wp = w + cg * CW;                                 // (wave-uniform: scalar loads)
+    const size_t row0 = ((size_t)n * Cq + cg * CW) * P + 2 * pair, goff = ((size_t)n * P + 2 * pair) * C + cg * CW;
     unsigned xv[CW];
     rt_u32x4 ga[CW / 8], gb[CW / 8];
     float mu0 = 0.f, mu1 = 0.f, r0 = 0.f, r1 = 0.f;
-    if (valid) {
+    if (valid && live > 0) {
 #pragma unroll
         for (int j = 0; j < CW / 8; ++j) { ga[j] = *(const rt_u32x4*)(gy + goff + j * 8); gb[j] = *(const rt_u32x4*)(gy + goff + C + j * 8); }
+        if constexpr (LD) { rt_mask_live<CW>(ga, live); rt_mask_live<CW>(gb, live); }       // the pad columns of g: cleared, not multiplied away
 #pragma unroll
-        for (int c = 0; c < CW; ++c) xv[c] = *(const unsigned*)(x + row0 + (size_t)c * P);
+        for (int c = 0; c < CW; ++c) { if (c < live) xv[c] = *(const unsigned*)(x + row0 + (size_t)c * P); else xv[c] = 0u; }
         const float2 m2 = *(const float2*)(mean + (size_t)n * P + 2 * pair), s2 = *(const float2*)(rstd + (size_t)n * P + 2 * pair);
         mu0 = m2.x; mu1 = m2.y; r0 = s2.x; r1 = s2.y;
     } else {                                                       // lanes past the image contribute zeros everywhere
@@ -639,11 +691,11 @@ __global__ __launch_bounds__(512) void ln_nchw_to_nhwc_bwd_chan_kernel(const uin
 #pragma unroll
         for (int c = 0; c < CW; ++c) xv[c] = 0u;
     }
-    const float* wp = w + cg * CW;                                 // (wave-uniform: scalar loads)
     float s10 = 0.f, s11 = 0.f, s20 = 0.f, s21 = 0.f;
 #pragma unroll
     for (int c = 0; c < CW; ++c) {
-        const float gw0 = RT_CH(ga[c >> 3], c & 7) * wp[c], gw1 = RT_CH(gb[c >> 3], c & 7) * wp[c];
+        const float wc = LD ? rt_rl(wv, c) : wp[c];
+        const float gw0 = RT_CH(ga[c >> 3], c & 7) * wc, gw1 = RT_CH(gb[c >> 3], c & 7) * wc;
         s10 += gw0; s11 += gw1;
         s20 += gw0 * ((rt_lo(xv[c]) - mu0) * r0); s21 += gw1 * ((rt_hi(xv[c]) - mu1) * r1);
     }
@@ -655,7 +707,7 @@ __global__ __launch_bounds__(512) void ln_nchw_to_nhwc_bwd_chan_kernel(const uin
     __syncthreads();
     float4 t = float4{0.f, 0.f, 0.f, 0.f};
     for (int k = 0; k < nw; ++k) { const float4 q = red[k][lane]; t.x += q.x; t.y += q.y; t.z += q.z; t.w += q.w; }
-    const float m10 = t.x / (float)C, m11 = t.y / (float)C, m20 = t.z / (float)C, m21 = t.w / (float)C;
+    const float m10 = t.x / (float)Cq, m11 = t.y / (float)Cq, m20 = t.z / (float)Cq, m21 = t.w / (float)Cq;
     float accw[CW / 4], accb[CW / 4];
 #pragma unroll
     for (int j = 0; j < CW / 8; ++j) {
@@ -663,10 +715,10 @@ __global__ __launch_bounds__(512) void ln_nchw_to_nhwc_bwd_chan_kernel(const uin
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const int c = j * 8 + k;
-            const float wc = wp[c];
+            const float wc = LD ? rt_rl(wv, c) : wp[c];
             const float g0 = RT_CH(ga[j], k), g1 = RT_CH(gb[j], k);
             const float xh0 = (rt_lo(xv[c]) - mu0) * r0, xh1 = (rt_hi(xv[c]) - mu1) * r1;
-            if (valid) *(unsigned*)(dx + row0 + (size_t)c * P) = rt_pack2(r0 * (g0 * wc - m10 - xh0 * m20), r1 * (g1 * wc - m11 - xh1 * m21));
+            if (valid && c < live) *(unsigned*)(dx + row0 + (size_t)c * P) = rt_pack2(r0 * (g0 * wc - m10 - xh0 * m20), r1 * (g1 * wc - m11 - xh1 * m21));
             tw[k] = g0 * xh0 + g1 * xh1; ts[k] = g0 + g1;
         }
         accw[2 * j] = rt_fold4(tw[0], tw[1], tw[2], tw[3]); accw[2 * j + 1] = rt_fold4(tw[4], tw[5], tw[6], tw[7]);
@@ -689,11 +741,11 @@ __global__ __launch_bounds__(512) void ln_nchw_to_nhwc_bwd_chan_kernel(const uin
 __device__ __forceinline__ float rt_ld16(const uint16_t* p) { return __uint_as_float((unsigned)*p << 16); }
 __device__ __forceinline__ uint16_t rt_bf(float v) { return (uint16_t)(rt_pack2(v, 0.f) & 0xffffu); }
 
-template <int CW>
+template <int CW, bool LD = false>
 __global__ __launch_bounds__(256) void scale_residual_fwd_chan1_kernel(const float* __restrict__ sc, const uint16_t* __restrict__ z,
                                                                        const float* __restrict__ gamma, const float* __restrict__ scale,
                                                                        float* __restrict__ out, uint16_t* __restrict__ out16,
-                                                                       int C, int P, int rounds, int nunits) {
+                                                                       int C, int P, int rounds, int nunits, int Cl) {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int unit = blockIdx.x * 4 + wave;                       // (image, channel group, round of 64 pixels)
     if (unit >= nunits) return;
@@ -701,50 +753,68 @@ __global__ __launch_bounds__(256) void scale_residual_fwd_chan1_kernel(const flo
     const int rd = unit % rounds, t = unit / rounds, cg = t % groups, n = t / groups;
     const int px = rd * 64 + lane;
     if (px >= P) return;
+    const int Cq = LD ? Cl : C, live = LD ? rt_live<CW>(Cl, cg) : CW;
+    if (LD && live == 0) return;                                  // a group of pad columns: nothing on the NCHW side
     const float sn = scale ? scale[n] : 1.0f;
     const uint16_t* zp = z + ((size_t)n * P + px) * C + cg * CW;
     rt_u32x4 za[CW / 8];
 #pragma unroll
     for (int j = 0; j < CW / 8; ++j) za[j] = *(const rt_u32x4*)(zp + j * 8);
-    const size_t row0 = ((size_t)n * C + cg * CW) * P + px;
+    const size_t row0 = ((size_t)n * Cq + cg * CW) * P + px;
     float sx[CW];
 #pragma unroll
-    for (int c = 0; c < CW; ++c) sx[c] = sc[row0 + (size_t)c * P];
+    for (int c = 0; c < CW; ++c) sx[c] = c < live ? sc[row0 + (size_t)c * P] : 0.f;
     const float* gp = gamma + cg * CW;
 #pragma unroll
     for (int c = 0; c < CW; ++c) {
+        if (c < live) {
         const float o = sx[c] + (gp[c] * sn) * RT_CH(za[c >> 3], c & 7);
         out[row0 + (size_t)c * P] = o;
         if (out16) out16[row0 + (size_t)c * P] = rt_bf(o);
+        }
     }
 }
 
-template <int CW>
-__global__ __launch_bounds__(256) void scale_residual_bwd_chan1_kernel(const float* __restrict__ dout, const uint16_t* __restrict__ dout16,
-                                                                       float* __restrict__ dsum, const uint16_t* __restrict__ z,
-                                                                       const float* __restrict__ gamma, const float* __restrict__ scale,
-                                                                       uint16_t* __restrict__ dz, float* __restrict__ part,
-                                                                       int C, int P, int rounds, int nunits) {
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int unit = blockIdx.x * 4 + wave;
-    if (unit >= nunits) return;
+// PART (LD only): the wave's group has fewer than CW live channels.  A pitched launch sends its full groups -- all but the last one or two -- through the
+// straight-line code of the plain kernel (only the row count of the NCHW tensors differs) and the others through the guarded one: behind a guarded
+// store the compiler waits for every outstanding memory operation, which made this bandwidth-bound kernel 5 us slower when every wave paid it.
+template <int CW, bool LD, bool PART>
+__device__ __forceinline__ void scale_residual_bwd_chan1_body(const float* __restrict__ dout, const uint16_t* __restrict__ dout16,
+                                                              float* __restrict__ dsum, const uint16_t* __restrict__ z,
+                                                              const float* __restrict__ gamma, const float* __restrict__ scale,
+                                                              uint16_t* __restrict__ dz, float* __restrict__ part,
+                                                              int C, int P, int rounds, int unit, int lane, int Cl) {
     const int groups = C / CW;
     const int rd = unit % rounds, t = unit / rounds, cg = t % groups, n = t / groups;
     const int px = rd * 64 + lane;
     const bool valid = px < P;
+    const int Cq = LD ? Cl : C, live = PART ? rt_live<CW>(Cl, cg) : CW;   // (a group of pad columns still writes its dz as +0)
+    const float gv = PART ? rt_lane_par<CW>(gamma, cg * CW, lane, Cl) : 0.f;
+    const float* gp = gamma + cg * CW;
     const float sn = scale ? scale[n] : 1.0f;
     const size_t zoff = ((size_t)n * P + px) * C + cg * CW;
-    const size_t row0 = ((size_t)n * C + cg * CW) * P + px;
+    const size_t row0 = ((size_t)n * Cq + cg * CW) * P + px;
     rt_u32x4 za[CW / 8];
     float vx[CW];
-    if (valid) {
+    if (valid && live > 0) {
 #pragma unroll
         for (int j = 0; j < CW / 8; ++j) za[j] = *(const rt_u32x4*)(z + zoff + j * 8);
+        if constexpr (PART) rt_mask_live<CW>(za, live);              // the pad columns of z: cleared, not multiplied away
 #pragma unroll
-        for (int c = 0; c < CW; ++c) vx[c] = dout[row0 + (size_t)c * P];
+        for (int c = 0; c < CW; ++c) vx[c] = c < live ? dout[row0 + (size_t)c * P] : 0.f;
         if (dout16) {
+            uint16_t hv[PART ? CW : 1];
 #pragma unroll
-            for (int c = 0; c < CW; ++c) { vx[c] += rt_ld16(dout16 + row0 + (size_t)c * P); dsum[row0 + (size_t)c * P] = vx[c]; }
+            for (int c = 0; c < CW; ++c) {
+                if constexpr (PART) {                              // (the load alone in its guarded block, its use behind all of them)
+                    uint16_t h = 0; if (c < live) h = dout16[row0 + (size_t)c * P];
+                    hv[c] = h;
+                } else { vx[c] += rt_ld16(dout16 + row0 + (size_t)c * P); dsum[row0 + (size_t)c * P] = vx[c]; }
+            }
+            if constexpr (PART) {
+#pragma unroll
+                for (int c = 0; c < CW; ++c) { vx[c] += __uint_as_float((unsigned)hv[c] << 16); if (c < live) dsum[row0 + (size_t)c * P] = vx[c]; }
+            }
         }
     } else {
 #pragma unroll
@@ -752,7 +822,6 @@ __global__ __launch_bounds__(256) void scale_residual_bwd_chan1_kernel(const flo
 #pragma unroll
         for (int c = 0; c < CW; ++c) vx[c] = 0.f;
     }
-    const float* gp = gamma + cg * CW;
     float accg[CW / 4], accs[CW / 4];
 #pragma unroll
     for (int j = 0; j < CW / 8; ++j) {
@@ -761,7 +830,7 @@ __global__ __launch_bounds__(256) void scale_residual_bwd_chan1_kernel(const flo
         for (int k = 0; k < 8; ++k) { d0[k] = vx[j * 8 + k] * sn; tg[k] = d0[k] * RT_CH(za[j], k); }
         rt_u32x4 oa;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) oa[k] = rt_pack2(gp[j * 8 + 2 * k] * d0[2 * k], gp[j * 8 + 2 * k + 1] * d0[2 * k + 1]);
+        for (int k = 0; k < 4; ++k) oa[k] = rt_pack2((PART ? rt_rl(gv, j * 8 + 2 * k) : gp[j * 8 + 2 * k]) * d0[2 * k], (PART ? rt_rl(gv, j * 8 + 2 * k + 1) : gp[j * 8 + 2 * k + 1]) * d0[2 * k + 1]);
         if (valid) *(rt_u32x4*)(dz + zoff + j * 8) = oa;
         accg[2 * j] = rt_fold4(tg[0], tg[1], tg[2], tg[3]); accg[2 * j + 1] = rt_fold4(tg[4], tg[5], tg[6], tg[7]);
         accs[2 * j] = rt_fold4(d0[0], d0[1], d0[2], d0[3]); accs[2 * j + 1] = rt_fold4(d0[4], d0[5], d0[6], d0[7]);
@@ -773,23 +842,47 @@ __global__ __launch_bounds__(256) void scale_residual_bwd_chan1_kernel(const flo
         float a = accg[m], b = accs[m];
 #pragma unroll
         for (int k = 1; k < 16; k <<= 1) { a += __shfl_xor(a, k, 64); b += __shfl_xor(b, k, 64); }
-        if ((lane & 15) == 0) { const int c = 4 * m + cofs; prow[c] = a; prow[C + c] = b * gp[c]; }
+        const float gc = PART ? __shfl(gv, 4 * m + cofs, 64) : 0.f;
+        if ((lane & 15) == 0) { const int c = 4 * m + cofs; prow[c] = a; prow[C + c] = b * (PART ? gc : gp[c]); }
     }
 }
+template <int CW, bool LD = false>
+__global__ __launch_bounds__(256) void scale_residual_bwd_chan1_kernel(const float* __restrict__ dout, const uint16_t* __restrict__ dout16,
+                                                                       float* __restrict__ dsum, const uint16_t* __restrict__ z,
+                                                                       const float* __restrict__ gamma, const float* __restrict__ scale,
+                                                                       uint16_t* __restrict__ dz, float* __restrict__ part,
+                                                                       int C, int P, int rounds, int nunits, int Cl) {
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int unit = blockIdx.x * 4 + wave;
+    if (unit >= nunits) return;
+    if constexpr (LD) {
+        if (rt_live<CW>(Cl, (unit / rounds) % (C / CW)) == CW) scale_residual_bwd_chan1_body<CW, true, false>(dout, dout16, dsum, z, gamma, scale, dz, part, C, P, rounds, unit, lane, Cl);
+        else scale_residual_bwd_chan1_body<CW, true, true>(dout, dout16, dsum, z, gamma, scale, dz, part, C, P, rounds, unit, lane, Cl);
+    } else scale_residual_bwd_chan1_body<CW, false, false>(dout, dout16, dsum, z, gamma, scale, dz, part, C, P, rounds, unit, lane, Cl);
+}
 
-template <int CW>
+// LD: every wave meets both barriers; a wave whose group is all pad columns adds zeros to the sums and writes its columns of y as +0.
+template <int CW, bool LD = false>
 __global__ __launch_bounds__(1024) void ln_nchw_to_nhwc_fwd_chan1_kernel(const uint16_t* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
                                                                          uint16_t* __restrict__ y, float* __restrict__ mean, float* __restrict__ rstd,
-                                                                         int C, int P, int rounds, float eps) {
+                                                                         int C, int P, int rounds, float eps, int Cl) {
     __shared__ float red[2][16][64];
     const int lane = threadIdx.x & 63, cg = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), nw = (int)(blockDim.x >> 6);
     const int rd = blockIdx.x % rounds, n = blockIdx.x / rounds;
     const int px = rd * 64 + lane;
     const bool valid = px < P;
-    const size_t row0 = ((size_t)n * C + cg * CW) * P + px, yoff = ((size_t)n * P + px) * C + cg * CW;
+    const int Cq = LD ? Cl : C, live = LD ? rt_live<CW>(Cl, cg) : CW;   // channel rows of the NCHW tensors; of this group
+    const size_t row0 = ((size_t)n * Cq + cg * CW) * P + px, yoff = ((size_t)n * P + px) * C + cg * CW;
     float v[CW];
 #pragma unroll
-    for (int c = 0; c < CW; ++c) v[c] = valid ? rt_ld16(x + row0 + (size_t)c * P) : 0.f;
+    for (int c = 0; c < CW; ++c) {
+        if constexpr (LD) { uint16_t h = 0; if (valid && c < live) h = x[row0 + (size_t)c * P]; v[c] = __uint_as_float((unsigned)h); }   // (raw: converted behind all the loads)
+        else v[c] = valid ? rt_ld16(x + row0 + (size_t)c * P) : 0.f;
+    }
+    if constexpr (LD) {
+#pragma unroll
+        for (int c = 0; c < CW; ++c) v[c] = __uint_as_float(__float_as_uint(v[c]) << 16);
+    }
     float s0 = 0.f;
 #pragma unroll
     for (int c = 0; c < CW; ++c) s0 += v[c];
@@ -797,15 +890,16 @@ __global__ __launch_bounds__(1024) void ln_nchw_to_nhwc_fwd_chan1_kernel(const u
     __syncthreads();
     float t0 = 0.f;
     for (int k = 0; k < nw; ++k) t0 += red[0][k][lane];
-    const float mu0 = t0 / (float)C;
+    const float mu0 = t0 / (float)Cq;
     float q0 = 0.f;
 #pragma unroll
-    for (int c = 0; c < CW; ++c) { const float a = v[c] - mu0; q0 += a * a; }
+    for (int c = 0; c < CW; ++c) { const float a = v[c] - mu0; if (c < live) q0 += a * a; }
     red[1][cg][lane] = q0;
     __syncthreads();
     t0 = 0.f;
     for (int k = 0; k < nw; ++k) t0 += red[1][k][lane];
-    const float r0 = 1.0f / sqrtf(t0 / (float)C + eps);
+    const float r0 = 1.0f / sqrtf(t0 / (float)Cq + eps);
+    const float wv = LD ? rt_lane_par<CW>(w, cg * CW, lane, Cl) : 0.f, bv = LD ? rt_lane_par<CW>(b, cg * CW, lane, Cl) : 0.f;   // (all lanes: read with v_readlane below)
     if (!valid) return;
     if (cg == 0) { mean[(size_t)n * P + px] = mu0; rstd[(size_t)n * P + px] = r0; }
     const float* wp = w + cg * CW; const float* bp = b + cg * CW;
@@ -815,46 +909,61 @@ __global__ __launch_bounds__(1024) void ln_nchw_to_nhwc_fwd_chan1_kernel(const u
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int c = j * 8 + 2 * k;
+            if constexpr (LD) {                                   // pad columns: +0, not (0 - mean) * rstd * w + b
+                const float y0 = c < live ? (v[c] - mu0) * r0 * rt_rl(wv, c) + rt_rl(bv, c) : 0.f;
+                const float y1 = c + 1 < live ? (v[c + 1] - mu0) * r0 * rt_rl(wv, c + 1) + rt_rl(bv, c + 1) : 0.f;
+                oa[k] = rt_pack2(y0, y1);
+            } else
             oa[k] = rt_pack2((v[c] - mu0) * r0 * wp[c] + bp[c], (v[c + 1] - mu0) * r0 * wp[c + 1] + bp[c + 1]);
         }
         *(rt_u32x4*)(y + yoff + j * 8) = oa;
     }
 }
 
-template <int CW>
+template <int CW, bool LD = false>
 __global__ __launch_bounds__(1024) void ln_nchw_to_nhwc_bwd_chan1_kernel(const uint16_t* __restrict__ gy, const uint16_t* __restrict__ x, const float* __restrict__ w,
                                                                          const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                                         uint16_t* __restrict__ dx, float* __restrict__ part, int C, int P, int rounds) {
+                                                                         uint16_t* __restrict__ dx, float* __restrict__ part, int C, int P, int rounds, int Cl) {
     __shared__ float2 red[16][64];
     const int lane = threadIdx.x & 63, cg = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), nw = (int)(blockDim.x >> 6);
     const int rd = blockIdx.x % rounds, n = blockIdx.x / rounds;
     const int px = rd * 64 + lane;
     const bool valid = px < P;
-    const size_t row0 = ((size_t)n * C + cg * CW) * P + px, goff = ((size_t)n * P + px) * C + cg * CW;
+    const int Cq = LD ? Cl : C, live = LD ? rt_live<CW>(Cl, cg) : CW;   // channel rows of the NCHW tensors; of this group (LD: every wave meets the barrier)
+    const size_t row0 = ((size_t)n * Cq + cg * CW) * P + px, goff = ((size_t)n * P + px) * C + cg * CW;
+    const float wv = LD ? rt_lane_par<CW>(w, cg * CW, lane, Cl) : 0.f;
+    const float* wp = w + cg * CW;
     float xh[CW];                                                  // normalised x
     rt_u32x4 ga[CW / 8];
     float r0 = 0.f;
     if (valid) {
 #pragma unroll
         for (int j = 0; j < CW / 8; ++j) ga[j] = *(const rt_u32x4*)(gy + goff + j * 8);
+        if constexpr (LD) rt_mask_live<CW>(ga, live);
         const float mu0 = mean[(size_t)n * P + px]; r0 = rstd[(size_t)n * P + px];
 #pragma unroll
-        for (int c = 0; c < CW; ++c) xh[c] = (rt_ld16(x + row0 + (size_t)c * P) - mu0) * r0;
+        for (int c = 0; c < CW; ++c) {
+            if constexpr (LD) { uint16_t h = 0; if (c < live) h = x[row0 + (size_t)c * P]; xh[c] = __uint_as_float((unsigned)h); }           // (raw: normalised behind all the loads)
+            else xh[c] = (rt_ld16(x + row0 + (size_t)c * P) - mu0) * r0;
+        }
+        if constexpr (LD) {
+#pragma unroll
+            for (int c = 0; c < CW; ++c) xh[c] = c < live ? (__uint_as_float(__float_as_uint(xh[c]) << 16) - mu0) * r0 : 0.f;
+        }
     } else {
 #pragma unroll
         for (int j = 0; j < CW / 8; ++j) ga[j] = rt_u32x4{0u, 0u, 0u, 0u};
 #pragma unroll
         for (int c = 0; c < CW; ++c) xh[c] = 0.f;
     }
-    const float* wp = w + cg * CW;
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
-    for (int c = 0; c < CW; ++c) { const float gw = RT_CH(ga[c >> 3], c & 7) * wp[c]; s1 += gw; s2 += gw * xh[c]; }
+    for (int c = 0; c < CW; ++c) { const float gw = RT_CH(ga[c >> 3], c & 7) * (LD ? rt_rl(wv, c) : wp[c]); s1 += gw; s2 += gw * xh[c]; }
     red[cg][lane] = float2{s1, s2};
     __syncthreads();
     float t1 = 0.f, t2 = 0.f;
     for (int k = 0; k < nw; ++k) { const float2 q = red[k][lane]; t1 += q.x; t2 += q.y; }
-    const float m1 = t1 / (float)C, m2 = t2 / (float)C;
+    const float m1 = t1 / (float)Cq, m2 = t2 / (float)Cq;
     float accw[CW / 4], accb[CW / 4];
 #pragma unroll
     for (int j = 0; j < CW / 8; ++j) {
@@ -863,7 +972,7 @@ __global__ __launch_bounds__(1024) void ln_nchw_to_nhwc_bwd_chan1_kernel(const u
         for (int k = 0; k < 8; ++k) {
             const int c = j * 8 + k;
             const float g0 = RT_CH(ga[j], k);
-            if (valid) dx[row0 + (size_t)c * P] = rt_bf(r0 * (g0 * wp[c] - m1 - xh[c] * m2));
+            if (valid && c < live) dx[row0 + (size_t)c * P] = rt_bf(r0 * (g0 * (LD ? rt_rl(wv, c) : wp[c]) - m1 - xh[c] * m2));
             tw[k] = g0 * xh[c]; ts[k] = g0;
         }
         accw[2 * j] = rt_fold4(tw[0], tw[1], tw[2], tw[3]); accw[2 * j + 1] = rt_fold4(tw[4], tw[5], tw[6], tw[7]);
@@ -956,28 +1065,62 @@ static int rt_chan_max_p() {                 // largest plane (pixels) the chann
     return v;
 }
 static bool rt_chan_waves() { static const bool v = slak_env_flag("SLAK_RT_CHAN", true); return v; }   // SLAK_RT_CHAN=0: small planes keep the pixel-tile residual kernel (A/B testing)
-template <int CW>
-static int launch_sr_fwd_chan(const float* sc, const uint16_t* z, const float* gamma, const float* scale, float* out, uint16_t* out16, int N, int C, int P, hipStream_t st) {
+// The launchers of the small-plane families.  C is the channel count the groups tile (the pitch of a pitched call), Cl the logical one; LD = (Cl != C).
+template <int CW, bool LD>
+static int launch_sr_fwd_chan(const float* sc, const uint16_t* z, const float* gamma, const float* scale, float* out, uint16_t* out16, int N, int Cl, int C, int P, hipStream_t st) {
     const int rounds = (P / 2 + 63) / 64, nunits = N * (C / CW) * rounds;
-    hipLaunchKernelGGL(scale_residual_fwd_chan_kernel<CW>, dim3((unsigned)((nunits + 3) / 4)), dim3(256), 0, st, sc, z, gamma, scale, out, out16, C, P, rounds, nunits);
+    hipLaunchKernelGGL((scale_residual_fwd_chan_kernel<CW, LD>), dim3((unsigned)((nunits + 3) / 4)), dim3(256), 0, st, sc, z, gamma, scale, out, out16, C, P, rounds, nunits, Cl);
     SLAK_LAUNCH_CHECK();
     return SLAK_OK;
 }
-template <int CW>
+template <int CW, bool LD>
 static int launch_sr_bwd_chan(const float* dout, const uint16_t* dout16, float* dsum, const uint16_t* z, const float* gamma, const float* scale,
-                              uint16_t* dz, float* part, int* rows, int N, int C, int P, hipStream_t st) {
+                              uint16_t* dz, float* part, int* rows, int N, int Cl, int C, int P, hipStream_t st) {
     const int rounds = (P / 2 + 63) / 64, nunits = N * (C / CW) * rounds;
-    hipLaunchKernelGGL(scale_residual_bwd_chan_kernel<CW>, dim3((unsigned)((nunits + 3) / 4)), dim3(256), 0, st, dout, dout16, dsum, z, gamma, scale, dz, part,
-                       C, P, rounds, nunits);
+    hipLaunchKernelGGL((scale_residual_bwd_chan_kernel<CW, LD>), dim3((unsigned)((nunits + 3) / 4)), dim3(256), 0, st, dout, dout16, dsum, z, gamma, scale, dz, part,
+                       C, P, rounds, nunits, Cl);
     SLAK_LAUNCH_CHECK();
     *rows = N * rounds;
     return SLAK_OK;
 }
-template <int CW>
+template <int CW, bool LD>
 static int launch_ln_bwd_chan(const uint16_t* g, const uint16_t* x, const float* w, const float* mean, const float* rstd, uint16_t* dx, float* part, int* rows,
-                              int N, int C, int P, hipStream_t st) {
+                              int N, int Cl, int C, int P, hipStream_t st) {
     const int rounds = (P / 2 + 63) / 64;
-    hipLaunchKernelGGL(ln_nchw_to_nhwc_bwd_chan_kernel<CW>, dim3((unsigned)(N * rounds)), dim3((unsigned)(C / CW * 64)), 0, st, g, x, w, mean, rstd, dx, part, C, P, rounds);
+    hipLaunchKernelGGL((ln_nchw_to_nhwc_bwd_chan_kernel<CW, LD>), dim3((unsigned)(N * rounds)), dim3((unsigned)(C / CW * 64)), 0, st, g, x, w, mean, rstd, dx, part, C, P, rounds, Cl);
+    SLAK_LAUNCH_CHECK();
+    *rows = N * rounds;
+    return SLAK_OK;
+}
+template <int CW, bool LD>
+static int launch_sr_fwd_chan1(const float* sc, const uint16_t* z, const float* gamma, const float* scale, float* out, uint16_t* out16, int N, int Cl, int C, int P, hipStream_t st) {
+    const int rounds = (P + 63) / 64, nunits = N * (C / CW) * rounds;
+    hipLaunchKernelGGL((scale_residual_fwd_chan1_kernel<CW, LD>), dim3((unsigned)((nunits + 3) / 4)), dim3(256), 0, st, sc, z, gamma, scale, out, out16, C, P, rounds, nunits, Cl);
+    SLAK_LAUNCH_CHECK();
+    return SLAK_OK;
+}
+template <int CW, bool LD>
+static int launch_sr_bwd_chan1(const float* dout, const uint16_t* dout16, float* dsum, const uint16_t* z, const float* gamma, const float* scale,
+                               uint16_t* dz, float* part, int* rows, int N, int Cl, int C, int P, hipStream_t st) {
+    const int rounds = (P + 63) / 64, nunits = N * (C / CW) * rounds;
+    hipLaunchKernelGGL((scale_residual_bwd_chan1_kernel<CW, LD>), dim3((unsigned)((nunits + 3) / 4)), dim3(256), 0, st, dout, dout16, dsum, z, gamma, scale, dz, part,
+                       C, P, rounds, nunits, Cl);
+    SLAK_LAUNCH_CHECK();
+    *rows = N * rounds;
+    return SLAK_OK;
+}
+template <int CW, bool LD>
+static int launch_ln_fwd_chan1(const uint16_t* x, const float* w, const float* b, uint16_t* y, float* mean, float* rstd, int N, int Cl, int C, int P, float eps, hipStream_t st) {
+    const int rounds = (P + 63) / 64;
+    hipLaunchKernelGGL((ln_nchw_to_nhwc_fwd_chan1_kernel<CW, LD>), dim3((unsigned)(N * rounds)), dim3((unsigned)(C / CW * 64)), 0, st, x, w, b, y, mean, rstd, C, P, rounds, eps, Cl);
+    SLAK_LAUNCH_CHECK();
+    return SLAK_OK;
+}
+template <int CW, bool LD>
+static int launch_ln_bwd_chan1(const uint16_t* g, const uint16_t* x, const float* w, const float* mean, const float* rstd, uint16_t* dx, float* part, int* rows,
+                               int N, int Cl, int C, int P, hipStream_t st) {
+    const int rounds = (P + 63) / 64;
+    hipLaunchKernelGGL((ln_nchw_to_nhwc_bwd_chan1_kernel<CW, LD>), dim3((unsigned)(N * rounds)), dim3((unsigned)(C / CW * 64)), 0, st, g, x, w, mean, rstd, dx, part, C, P, rounds, Cl);
     SLAK_LAUNCH_CHECK();
     *rows = N * rounds;
     return SLAK_OK;
@@ -1011,26 +1154,103 @@ static bool rt_wide_lanes() { static const bool v = slak_env_flag("SLAK_RT_WIDE"
         case 512: { CALL(64, 8); }                \
         default: return SLAK_ERR_UNSUPPORTED;     \
     }
+static bool rt_reg_has(int C, int P) { return !(P & 1) && (C == 64 || C == 96 || C == 128 || C == 192 || C == 256 || C == 384 || C == 512); }
+// The pitched calls (slak_*_ld): Cl channel rows on the NCHW side, rows of ldc on the NHWC side.  The pixel-pair kernels on the
+// instantiation whose C IS the pitch (128 / 256 / 512: Cl = 124 / 249 / 499 of the width-1.3 models), even planes, at most RT_LD_PAD pad columns; SLAK_ERR_UNSUPPORTED elsewhere
+// (the caller runs the LDS-tile kernels of block_tail.hip).  The partial rows are 2 * ldc wide: [0, Cl) and [ldc, ldc + Cl) are the logical columns.
+#define SLAK_RT_DISPATCH_LD(LDC, CALL)            \
+    if ((P & 1) || Cl > LDC || LDC - Cl > RT_LD_PAD) return SLAK_ERR_UNSUPPORTED; \
+    switch (LDC) {                                \
+        case 128: { CALL(64, 2); }                \
+        case 256: { CALL(64, 4); }                \
+        case 512: { CALL(64, 8); }                \
+        default: return SLAK_ERR_UNSUPPORTED;     \
+    }
+static bool rt_reg_ld_has(int Cl, int ldc, int P) { return !(P & 1) && Cl <= ldc && ldc - Cl <= RT_LD_PAD && (ldc == 128 || ldc == 256 || ldc == 512); }
 
-int launch_ln_nchw_to_nhwc_fwd_reg(const void* x, const float* w, const float* b, void* y, float* mean, float* rstd, int N, int C, int P, float eps, hipStream_t st) {
-    { const int cw1 = rt_chan1_cw(C, P, N, 16), rounds = (P + 63) / 64;
-      if (cw1 == 48) { hipLaunchKernelGGL(ln_nchw_to_nhwc_fwd_chan1_kernel<48>, dim3((unsigned)(N * rounds)), dim3((unsigned)(C / 48 * 64)), 0, st, (const uint16_t*)x, w, b, (uint16_t*)y, mean, rstd, C, P, rounds, eps); SLAK_LAUNCH_CHECK(); return SLAK_OK; }
-      if (cw1 == 32) { hipLaunchKernelGGL(ln_nchw_to_nhwc_fwd_chan1_kernel<32>, dim3((unsigned)(N * rounds)), dim3((unsigned)(C / 32 * 64)), 0, st, (const uint16_t*)x, w, b, (uint16_t*)y, mean, rstd, C, P, rounds, eps); SLAK_LAUNCH_CHECK(); return SLAK_OK; } }
+// WHICH family runs op (SLAK_TAIL_*) on (N, Cl, ldc, P), and with how many channels per wave: the one decision that the eight launchers below and
+// slak_block_tail_family share.  Host code only, no device call.  Cl == ldc is a plain call.  A pitched call takes the small-plane families exactly
+// where the plain call on C = ldc takes them (the predicates see the pitch: the groups tile it), ahead of the pixel-pair kernels; one rung is the
+// pitched calls' own: the LayerNorm kernels on odd planes with 64 channels per wave where 48 / 32 would need more than 16 waves (ldc = 1024: C = 998).
+// SLAK_TAIL_FAMILY_NONE: no kernel of this file (the caller runs the LDS-tile kernels of block_tail.hip).
+RtChoice rt_tail_choice(int op, int sc_dtype, int N, int Cl, int ldc, int P) {
+    const bool ld = Cl != ldc;
+    const bool small_even = !(P & 1) && P <= rt_chan_max_p() && rt_chan_waves();
+    int cw = 0;
+    switch (op) {
+        case SLAK_TAIL_LN_FWD: case SLAK_TAIL_LN_BWD:
+            cw = rt_chan1_cw(ldc, P, N, 16);
+            if (!cw && ld && ldc % 64 == 0 && ldc / 64 <= 16 && rt_chan1_cw(64, P, N, 16)) cw = 64;
+            if (cw) return RtChoice{SLAK_TAIL_FAMILY_CHAN1, cw};
+            if (op == SLAK_TAIL_LN_BWD && (cw = rt_ln_chan_cw(ldc, P, N))) return RtChoice{SLAK_TAIL_FAMILY_CHAN, cw};
+            break;
+        case SLAK_TAIL_SR_FWD:
+            if (sc_dtype != SLAK_F32 && sc_dtype != SLAK_BF16) return RtChoice{SLAK_TAIL_FAMILY_NONE, 0};
+            if (sc_dtype == SLAK_F32) {
+                if ((cw = rt_chan1_cw(ldc, P, N, 1 << 20))) return RtChoice{SLAK_TAIL_FAMILY_CHAN1, cw};      // odd planes: one pixel per lane
+                if (small_even && (cw = ldc % 48 == 0 ? 48 : ldc % 64 == 0 ? 64 : 0)) return RtChoice{SLAK_TAIL_FAMILY_CHAN, cw};   // small planes: a wave per (image, channel group)
+            }
+            break;
+        case SLAK_TAIL_SR_BWD:
+            if ((cw = rt_chan1_cw(ldc, P, N, 1 << 20))) return RtChoice{SLAK_TAIL_FAMILY_CHAN1, cw};
+            if (small_even && (long long)N * ((P / 2 + 63) / 64) <= 8192 && (cw = ldc % 24 == 0 ? 24 : ldc % 32 == 0 ? 32 : 0))   // rows <= the workspace's 8192
+                return RtChoice{SLAK_TAIL_FAMILY_CHAN, cw};
+            break;
+        default: return RtChoice{SLAK_TAIL_FAMILY_NONE, 0};
+    }
+    return RtChoice{(ld ? rt_reg_ld_has(Cl, ldc, P) : rt_reg_has(ldc, P)) ? SLAK_TAIL_FAMILY_REG : SLAK_TAIL_FAMILY_NONE, 0};
+}
+// family F's launcher on the chosen channels per wave, plain or pitched instantiation
+#define SLAK_RT_CW(CWV, FN, ...) if (ch.cw == CWV) return ld ? FN<CWV, true>(__VA_ARGS__) : FN<CWV, false>(__VA_ARGS__);
+#define SLAK_RT_CW_LD(CWV, FN, ...) if (ch.cw == CWV && ld) return FN<CWV, true>(__VA_ARGS__);
+
+int launch_ln_nchw_to_nhwc_fwd_reg_ld(const void* x, const float* w, const float* b, void* y, float* mean, float* rstd, int N, int Cl, int ldc, int P, float eps, hipStream_t st) {
+    const RtChoice ch = rt_tail_choice(SLAK_TAIL_LN_FWD, 0, N, Cl, ldc, P);
+    const bool ld = Cl != ldc;
+    if (ch.family == SLAK_TAIL_FAMILY_CHAN1) {
+        SLAK_RT_CW(48, launch_ln_fwd_chan1, (const uint16_t*)x, w, b, (uint16_t*)y, mean, rstd, N, Cl, ldc, P, eps, st)
+        SLAK_RT_CW(32, launch_ln_fwd_chan1, (const uint16_t*)x, w, b, (uint16_t*)y, mean, rstd, N, Cl, ldc, P, eps, st)
+        SLAK_RT_CW_LD(64, launch_ln_fwd_chan1, (const uint16_t*)x, w, b, (uint16_t*)y, mean, rstd, N, Cl, ldc, P, eps, st)
+    }
+    if (ch.family != SLAK_TAIL_FAMILY_REG) return SLAK_ERR_UNSUPPORTED;
+    if (ld) {
+#define CALL(CL, G) return (launch_ln_fwd_reg<CL, G, false, false, true>((const uint16_t*)x, w, b, (uint16_t*)y, mean, rstd, N, P, eps, st, 0, Cl))
+        SLAK_RT_DISPATCH_LD(ldc, CALL)
+#undef CALL
+    }
 #define CALL(CL, G) return launch_ln_fwd_reg<CL, G>((const uint16_t*)x, w, b, (uint16_t*)y, mean, rstd, N, P, eps, st)
-    SLAK_RT_DISPATCH(C, CALL)
+    SLAK_RT_DISPATCH(ldc, CALL)
+#undef CALL
+}
+int launch_ln_nchw_to_nhwc_fwd_reg(const void* x, const float* w, const float* b, void* y, float* mean, float* rstd, int N, int C, int P, float eps, hipStream_t st) {
+    return launch_ln_nchw_to_nhwc_fwd_reg_ld(x, w, b, y, mean, rstd, N, C, C, P, eps, st);
+}
+int launch_ln_nchw_to_nhwc_bwd_reg_ld(const void* g, const void* x, const float* w, const float* mean, const float* rstd, void* dx, float* part, int* rows,
+                                      int N, int Cl, int ldc, int P, hipStream_t st) {
+    const RtChoice ch = rt_tail_choice(SLAK_TAIL_LN_BWD, 0, N, Cl, ldc, P);
+    const bool ld = Cl != ldc;
+    if (ch.family == SLAK_TAIL_FAMILY_CHAN1) {
+        SLAK_RT_CW(48, launch_ln_bwd_chan1, (const uint16_t*)g, (const uint16_t*)x, w, mean, rstd, (uint16_t*)dx, part, rows, N, Cl, ldc, P, st)
+        SLAK_RT_CW(32, launch_ln_bwd_chan1, (const uint16_t*)g, (const uint16_t*)x, w, mean, rstd, (uint16_t*)dx, part, rows, N, Cl, ldc, P, st)
+        SLAK_RT_CW_LD(64, launch_ln_bwd_chan1, (const uint16_t*)g, (const uint16_t*)x, w, mean, rstd, (uint16_t*)dx, part, rows, N, Cl, ldc, P, st)
+    }
+    if (ch.family == SLAK_TAIL_FAMILY_CHAN) {
+        SLAK_RT_CW(48, launch_ln_bwd_chan, (const uint16_t*)g, (const uint16_t*)x, w, mean, rstd, (uint16_t*)dx, part, rows, N, Cl, ldc, P, st)
+        SLAK_RT_CW(64, launch_ln_bwd_chan, (const uint16_t*)g, (const uint16_t*)x, w, mean, rstd, (uint16_t*)dx, part, rows, N, Cl, ldc, P, st)
+    }
+    if (ch.family != SLAK_TAIL_FAMILY_REG) return SLAK_ERR_UNSUPPORTED;
+    if (ld) {
+#define CALL(CL, G) return (launch_ln_bwd_reg<CL, G, false, false, true>((const uint16_t*)g, (const uint16_t*)x, w, mean, rstd, (uint16_t*)dx, part, rows, N, P, st, 0, Cl))
+        SLAK_RT_DISPATCH_LD(ldc, CALL)
+#undef CALL
+    }
+#define CALL(CL, G) return launch_ln_bwd_reg<CL, G>((const uint16_t*)g, (const uint16_t*)x, w, mean, rstd, (uint16_t*)dx, part, rows, N, P, st)
+    SLAK_RT_DISPATCH(ldc, CALL)
 #undef CALL
 }
 int launch_ln_nchw_to_nhwc_bwd_reg(const void* g, const void* x, const float* w, const float* mean, const float* rstd, void* dx, float* part, int* rows,
                                    int N, int C, int P, hipStream_t st) {
-    { const int cw1 = rt_chan1_cw(C, P, N, 16), rounds = (P + 63) / 64;
-      if (cw1 == 48) { hipLaunchKernelGGL(ln_nchw_to_nhwc_bwd_chan1_kernel<48>, dim3((unsigned)(N * rounds)), dim3((unsigned)(C / 48 * 64)), 0, st, (const uint16_t*)g, (const uint16_t*)x, w, mean, rstd, (uint16_t*)dx, part, C, P, rounds); SLAK_LAUNCH_CHECK(); *rows = N * rounds; return SLAK_OK; }
-      if (cw1 == 32) { hipLaunchKernelGGL(ln_nchw_to_nhwc_bwd_chan1_kernel<32>, dim3((unsigned)(N * rounds)), dim3((unsigned)(C / 32 * 64)), 0, st, (const uint16_t*)g, (const uint16_t*)x, w, mean, rstd, (uint16_t*)dx, part, C, P, rounds); SLAK_LAUNCH_CHECK(); *rows = N * rounds; return SLAK_OK; } }
-    { const int cw = rt_ln_chan_cw(C, P, N);
-      if (cw == 48) return launch_ln_bwd_chan<48>((const uint16_t*)g, (const uint16_t*)x, w, mean, rstd, (uint16_t*)dx, part, rows, N, C, P, st);
-      if (cw == 64) return launch_ln_bwd_chan<64>((const uint16_t*)g, (const uint16_t*)x, w, mean, rstd, (uint16_t*)dx, part, rows, N, C, P, st); }
-#define CALL(CL, G) return launch_ln_bwd_reg<CL, G>((const uint16_t*)g, (const uint16_t*)x, w, mean, rstd, (uint16_t*)dx, part, rows, N, P, st)
-    SLAK_RT_DISPATCH(C, CALL)
-#undef CALL
+    return launch_ln_nchw_to_nhwc_bwd_reg_ld(g, x, w, mean, rstd, dx, part, rows, N, C, C, P, st);
 }
 // LayerNorm(channels_first) of an fp32 NCHW tensor written as the bf16 patch matrix of a 2x2 / stride-2 convolution, and its backward
 int launch_ln_patch_fwd_reg(const float* x, const float* w, const float* b, void* a, float* mean, float* rstd, int N, int C, int H, int W, float eps, hipStream_t st) {
@@ -1048,83 +1268,72 @@ int launch_ln_patch_bwd_reg(const void* g, const float* x, const float* w, const
     SLAK_RT_DISPATCH(C, CALL)
 #undef CALL
 }
-int launch_scale_residual_fwd_reg(const void* sc, int sc_dtype, const void* z, const float* gamma, const float* scale, float* out, void* out16,
-                                  int N, int C, int P, hipStream_t st) {
+int launch_scale_residual_fwd_reg_ld(const void* sc, int sc_dtype, const void* z, const float* gamma, const float* scale, float* out, void* out16,
+                                     int N, int Cl, int ldc, int P, hipStream_t st) {
+    const RtChoice ch = rt_tail_choice(SLAK_TAIL_SR_FWD, sc_dtype, N, Cl, ldc, P);
+    const bool ld = Cl != ldc;
+    if (ch.family == SLAK_TAIL_FAMILY_CHAN1) {
+        SLAK_RT_CW(48, launch_sr_fwd_chan1, (const float*)sc, (const uint16_t*)z, gamma, scale, out, (uint16_t*)out16, N, Cl, ldc, P, st)
+        SLAK_RT_CW(32, launch_sr_fwd_chan1, (const float*)sc, (const uint16_t*)z, gamma, scale, out, (uint16_t*)out16, N, Cl, ldc, P, st)
+    }
+    if (ch.family == SLAK_TAIL_FAMILY_CHAN) {
+        SLAK_RT_CW(48, launch_sr_fwd_chan, (const float*)sc, (const uint16_t*)z, gamma, scale, out, (uint16_t*)out16, N, Cl, ldc, P, st)
+        SLAK_RT_CW(64, launch_sr_fwd_chan, (const float*)sc, (const uint16_t*)z, gamma, scale, out, (uint16_t*)out16, N, Cl, ldc, P, st)
+    }
+    if (ch.family != SLAK_TAIL_FAMILY_REG) return SLAK_ERR_UNSUPPORTED;
     if (sc_dtype == SLAK_F32) {
+        if (ld) {
+#define CALL(CL, G) return (launch_sr_fwd_reg<CL, G, float, true>((const float*)sc, (const uint16_t*)z, gamma, scale, out, (uint16_t*)out16, N, P, st, Cl))
+            SLAK_RT_DISPATCH_LD(ldc, CALL)
+#undef CALL
+        }
 #define CALL(CL, G) return launch_sr_fwd_reg<CL, G, float>((const float*)sc, (const uint16_t*)z, gamma, scale, out, (uint16_t*)out16, N, P, st)
         // C = 384: 96 channels per lane on 4 lanes per pixel pair double the length of a wave's NCHW row segments (64 -> 128 bytes); the
         // forward residual kernel is the one of the four whose registers allow it without spilling
-        { const int cw1 = rt_chan1_cw(C, P, N, 1 << 20), rounds = (P + 63) / 64;      // odd planes: one pixel per lane
-          if (cw1 == 48) { const int nu = N * (C / 48) * rounds; hipLaunchKernelGGL(scale_residual_fwd_chan1_kernel<48>, dim3((unsigned)((nu + 3) / 4)), dim3(256), 0, st, (const float*)sc, (const uint16_t*)z, gamma, scale, out, (uint16_t*)out16, C, P, rounds, nu); SLAK_LAUNCH_CHECK(); return SLAK_OK; }
-          if (cw1 == 32) { const int nu = N * (C / 32) * rounds; hipLaunchKernelGGL(scale_residual_fwd_chan1_kernel<32>, dim3((unsigned)((nu + 3) / 4)), dim3(256), 0, st, (const float*)sc, (const uint16_t*)z, gamma, scale, out, (uint16_t*)out16, C, P, rounds, nu); SLAK_LAUNCH_CHECK(); return SLAK_OK; } }
-        if (!(P & 1) && P <= rt_chan_max_p() && rt_chan_waves()) {              // small planes: a wave per (image, channel group)
-            if (C % 48 == 0) return launch_sr_fwd_chan<48>((const float*)sc, (const uint16_t*)z, gamma, scale, out, (uint16_t*)out16, N, C, P, st);
-            if (C % 64 == 0) return launch_sr_fwd_chan<64>((const float*)sc, (const uint16_t*)z, gamma, scale, out, (uint16_t*)out16, N, C, P, st);
-        }
-        if (C == 384 && !(P & 1) && rt_wide_lanes()) { CALL(96, 4); }
-        SLAK_RT_DISPATCH(C, CALL)
+        if (ldc == 384 && !(P & 1) && rt_wide_lanes()) { CALL(96, 4); }
+        SLAK_RT_DISPATCH(ldc, CALL)
 #undef CALL
     } else if (sc_dtype == SLAK_BF16) {
-#define CALL(CL, G) return launch_sr_fwd_reg<CL, G, bf16_t>((const bf16_t*)sc, (const uint16_t*)z, gamma, scale, out, (uint16_t*)out16, N, P, st)
-        SLAK_RT_DISPATCH(C, CALL)
-#undef CALL
-    }
-    return SLAK_ERR_UNSUPPORTED;
-}
-int launch_scale_residual_bwd_reg(const float* dout, const void* dout16, float* dsum, const void* z, const float* gamma, const float* scale, void* dz,
-                                  float* part, int* rows, int N, int C, int P, hipStream_t st) {
-    { const int cw1 = rt_chan1_cw(C, P, N, 1 << 20), rounds = (P + 63) / 64;          // odd planes: one pixel per lane
-      if (cw1 == 48) { const int nu = N * (C / 48) * rounds; hipLaunchKernelGGL(scale_residual_bwd_chan1_kernel<48>, dim3((unsigned)((nu + 3) / 4)), dim3(256), 0, st, dout, (const uint16_t*)dout16, dsum, (const uint16_t*)z, gamma, scale, (uint16_t*)dz, part, C, P, rounds, nu); SLAK_LAUNCH_CHECK(); *rows = N * rounds; return SLAK_OK; }
-      if (cw1 == 32) { const int nu = N * (C / 32) * rounds; hipLaunchKernelGGL(scale_residual_bwd_chan1_kernel<32>, dim3((unsigned)((nu + 3) / 4)), dim3(256), 0, st, dout, (const uint16_t*)dout16, dsum, (const uint16_t*)z, gamma, scale, (uint16_t*)dz, part, C, P, rounds, nu); SLAK_LAUNCH_CHECK(); *rows = N * rounds; return SLAK_OK; } }
-    if (!(P & 1) && P <= rt_chan_max_p() && (long long)N * ((P / 2 + 63) / 64) <= 8192 && rt_chan_waves()) {     // small planes: a wave per (image, channel group); rows <= the workspace's 8192
-        if (C % 24 == 0) return launch_sr_bwd_chan<24>(dout, (const uint16_t*)dout16, dsum, (const uint16_t*)z, gamma, scale, (uint16_t*)dz, part, rows, N, C, P, st);
-        if (C % 32 == 0) return launch_sr_bwd_chan<32>(dout, (const uint16_t*)dout16, dsum, (const uint16_t*)z, gamma, scale, (uint16_t*)dz, part, rows, N, C, P, st);
-    }
-#define CALL(CL, G) return launch_sr_bwd_reg<CL, G>(dout, (const uint16_t*)dout16, dsum, (const uint16_t*)z, gamma, scale, (uint16_t*)dz, part, rows, N, P, st)
-    SLAK_RT_DISPATCH(C, CALL)
-#undef CALL
-}
-
-// ---- the pitched entry points (slak_*_ld): Cl channel rows on the NCHW side, rows of ldc on the NHWC side.  The pixel-pair kernels above on the
-// instantiation whose C IS the pitch (128 / 256 / 512: Cl = 124 / 249 / 499 of the width-1.3 models), even planes, at most RT_LD_PAD pad columns; SLAK_ERR_UNSUPPORTED elsewhere
-// (the caller runs the LDS-tile kernels of block_tail.hip).  The partial rows are 2 * ldc wide: [0, Cl) and [ldc, ldc + Cl) are the logical columns.
-#define SLAK_RT_DISPATCH_LD(LDC, CALL)            \
-    if ((P & 1) || Cl > LDC || LDC - Cl > RT_LD_PAD) return SLAK_ERR_UNSUPPORTED; \
-    switch (LDC) {                                \
-        case 128: { CALL(64, 2); }                \
-        case 256: { CALL(64, 4); }                \
-        case 512: { CALL(64, 8); }                \
-        default: return SLAK_ERR_UNSUPPORTED;     \
-    }
-int launch_ln_nchw_to_nhwc_fwd_reg_ld(const void* x, const float* w, const float* b, void* y, float* mean, float* rstd, int N, int Cl, int ldc, int P, float eps, hipStream_t st) {
-#define CALL(CL, G) return (launch_ln_fwd_reg<CL, G, false, false, true>((const uint16_t*)x, w, b, (uint16_t*)y, mean, rstd, N, P, eps, st, 0, Cl))
-    SLAK_RT_DISPATCH_LD(ldc, CALL)
-#undef CALL
-}
-int launch_ln_nchw_to_nhwc_bwd_reg_ld(const void* g, const void* x, const float* w, const float* mean, const float* rstd, void* dx, float* part, int* rows,
-                                      int N, int Cl, int ldc, int P, hipStream_t st) {
-#define CALL(CL, G) return (launch_ln_bwd_reg<CL, G, false, false, true>((const uint16_t*)g, (const uint16_t*)x, w, mean, rstd, (uint16_t*)dx, part, rows, N, P, st, 0, Cl))
-    SLAK_RT_DISPATCH_LD(ldc, CALL)
-#undef CALL
-}
-int launch_scale_residual_fwd_reg_ld(const void* sc, int sc_dtype, const void* z, const float* gamma, const float* scale, float* out, void* out16,
-                                     int N, int Cl, int ldc, int P, hipStream_t st) {
-    if (sc_dtype == SLAK_F32) {
-#define CALL(CL, G) return (launch_sr_fwd_reg<CL, G, float, true>((const float*)sc, (const uint16_t*)z, gamma, scale, out, (uint16_t*)out16, N, P, st, Cl))
-        SLAK_RT_DISPATCH_LD(ldc, CALL)
-#undef CALL
-    } else if (sc_dtype == SLAK_BF16) {
+        if (ld) {
 #define CALL(CL, G) return (launch_sr_fwd_reg<CL, G, bf16_t, true>((const bf16_t*)sc, (const uint16_t*)z, gamma, scale, out, (uint16_t*)out16, N, P, st, Cl))
-        SLAK_RT_DISPATCH_LD(ldc, CALL)
+            SLAK_RT_DISPATCH_LD(ldc, CALL)
+#undef CALL
+        }
+#define CALL(CL, G) return launch_sr_fwd_reg<CL, G, bf16_t>((const bf16_t*)sc, (const uint16_t*)z, gamma, scale, out, (uint16_t*)out16, N, P, st)
+        SLAK_RT_DISPATCH(ldc, CALL)
 #undef CALL
     }
     return SLAK_ERR_UNSUPPORTED;
+}
+int launch_scale_residual_fwd_reg(const void* sc, int sc_dtype, const void* z, const float* gamma, const float* scale, float* out, void* out16,
+                                  int N, int C, int P, hipStream_t st) {
+    return launch_scale_residual_fwd_reg_ld(sc, sc_dtype, z, gamma, scale, out, out16, N, C, C, P, st);
 }
 int launch_scale_residual_bwd_reg_ld(const float* dout, const void* dout16, float* dsum, const void* z, const float* gamma, const float* scale, void* dz,
                                      float* part, int* rows, int N, int Cl, int ldc, int P, hipStream_t st) {
+    const RtChoice ch = rt_tail_choice(SLAK_TAIL_SR_BWD, 0, N, Cl, ldc, P);
+    const bool ld = Cl != ldc;
+    if (ch.family == SLAK_TAIL_FAMILY_CHAN1) {
+        SLAK_RT_CW(48, launch_sr_bwd_chan1, dout, (const uint16_t*)dout16, dsum, (const uint16_t*)z, gamma, scale, (uint16_t*)dz, part, rows, N, Cl, ldc, P, st)
+        SLAK_RT_CW(32, launch_sr_bwd_chan1, dout, (const uint16_t*)dout16, dsum, (const uint16_t*)z, gamma, scale, (uint16_t*)dz, part, rows, N, Cl, ldc, P, st)
+    }
+    if (ch.family == SLAK_TAIL_FAMILY_CHAN) {
+        SLAK_RT_CW(24, launch_sr_bwd_chan, dout, (const uint16_t*)dout16, dsum, (const uint16_t*)z, gamma, scale, (uint16_t*)dz, part, rows, N, Cl, ldc, P, st)
+        SLAK_RT_CW(32, launch_sr_bwd_chan, dout, (const uint16_t*)dout16, dsum, (const uint16_t*)z, gamma, scale, (uint16_t*)dz, part, rows, N, Cl, ldc, P, st)
+    }
+    if (ch.family != SLAK_TAIL_FAMILY_REG) return SLAK_ERR_UNSUPPORTED;
+    if (ld) {
 #define CALL(CL, G) return (launch_sr_bwd_reg<CL, G, true>(dout, (const uint16_t*)dout16, dsum, (const uint16_t*)z, gamma, scale, (uint16_t*)dz, part, rows, N, P, st, Cl))
-    SLAK_RT_DISPATCH_LD(ldc, CALL)
+        SLAK_RT_DISPATCH_LD(ldc, CALL)
 #undef CALL
+    }
+#define CALL(CL, G) return launch_sr_bwd_reg<CL, G>(dout, (const uint16_t*)dout16, dsum, (const uint16_t*)z, gamma, scale, (uint16_t*)dz, part, rows, N, P, st)
+    SLAK_RT_DISPATCH(ldc, CALL)
+#undef CALL
+}
+int launch_scale_residual_bwd_reg(const float* dout, const void* dout16, float* dsum, const void* z, const float* gamma, const float* scale, void* dz,
+                                  float* part, int* rows, int N, int C, int P, hipStream_t st) {
+    return launch_scale_residual_bwd_reg_ld(dout, dout16, dsum, z, gamma, scale, dz, part, rows, N, C, C, P, st);
 }
 
 }  // namespace slak

@@ -12,6 +12,12 @@
 // The caches below are shared by the forward (caller thread) and the backward (autograd's device threads, possibly one per GPU in a single process):
 // one mutex guards their lookups / inserts; entries are never erased, so references stay valid after the lock is dropped.
 //
+// Pitched blocks (odd C of the width-1.3 models, or an even width under block_ops.pad_even_widths): the NHWC intermediates t, y1, a, z and their gradients
+// have rows of `ldc` > C elements, the caller hands in the zero-padded bf16 operands block_ops._pitched_operands builds (W1 [4 ldc][ldc], W2 [ldc][4 ldc], both
+// transposes, b1, b2).  The convs and BatchNorms run on the logical C (any parity), the MLP on (M, 4 ldc, ldc), the tail through the slak_*_ld entry points;
+// the backward cuts dW1, db1, dW2 back to the parameters' shapes.  The launches are those of the Python sequence on the same operands: bit-identical results
+// (tests/test_pitched_runner_gpu.py).  ldc == C is the plain block, launch for launch what it was.
+//
 // block_forward returns an EMPTY list when a precondition of the one-launch path does not hold for the shape (no three-branch forward with
 // statistics / data gradient / weight gradient launch): the caller (block_ops._BlockFn) then runs the Python sequence, which knows every fallback.
 #include <torch/extension.h>
@@ -111,13 +117,13 @@ Side& side_of(int dev) {
     return m.emplace(dev, s).first->second;
 }
 
-struct Shape { int N, C, H, W, K, P, M, C4; };
+struct Shape { int N, C, H, W, K, P, M, C4, Cp; };                  // Cp: the row pitch of the NHWC tensors (== C: a plain block); C4: rows of W1 as handed in (4 Cp)
 
 // what the library answers for a block shape, asked once
 struct Plan { bool ok; int rows; size_t ws; bool nt1, nt2, ntd1, ntd2, wg1, wg2, bwd1, gbwd, mlp1, gg1, gg2; size_t off[5], len[5]; };   // off/len: the backward's deferred-reduction regions behind the common scratch
 const Plan& plan_of(const Shape& s) {
     static std::map<std::vector<int>, Plan> cache;
-    const std::vector<int> key = {s.N, s.C, s.H, s.W, s.K, s.C4};
+    const std::vector<int> key = {s.N, s.C, s.H, s.W, s.K, s.C4, s.Cp};
     std::lock_guard<std::mutex> lk(g_cache_mu);
     auto it = cache.find(key);
     if (it != cache.end()) return it->second;
@@ -126,33 +132,39 @@ const Plan& plan_of(const Shape& s) {
     p.rows = slak_dwconv2d_tri_stats_rows(dt, s.N, s.C, s.H, s.W, s.K);
     const size_t wtri = slak_dwconv2d_tri_filter_workspace_bytes(dt, s.N, s.C, s.H, s.W, s.K);
     p.ok = slak_dwconv2d_tri_supported_op(dt, s.N, s.C, s.H, s.W, s.K, 0) == 1 && slak_dwconv2d_tri_supported_op(dt, s.N, s.C, s.H, s.W, s.K, 1) == 1 &&
-           p.rows > 0 && wtri > 0 && (s.C % 2) == 0 && s.C <= 1024;
-    p.nt1 = slak_linear_nt_supported(s.M, s.C4, s.C, 1) != 0;      // pwconv1 + GELU in one streaming pass
-    p.nt2 = slak_linear_nt_supported(s.M, s.C, s.C4, 0) != 0;      // pwconv2
-    p.ntd1 = slak_linear_nt_supported(s.M, s.C4, s.C, 0) != 0;     // dz W2
-    p.ntd2 = slak_linear_nt_supported(s.M, s.C, s.C4, 0) != 0;     // dy1 W1
-    p.wg1 = slak_linear_wgrad_supported(s.M, s.C4, s.C) != 0;      // dW1 = dy1^T t
-    p.wg2 = slak_linear_wgrad_supported(s.M, s.C, s.C4) != 0;      // dW2 = dz^T a
+           p.rows > 0 && wtri > 0;
+    if (s.Cp == s.C) p.ok = p.ok && (s.C % 2) == 0 && s.C <= 1024;
+    else {                                                         // pitched: any parity of C; every tail op must have a kernel for (C, ldc)
+        p.ok = p.ok && s.Cp > s.C && s.Cp % 8 == 0 && s.Cp <= 1024 && s.C4 == 4 * s.Cp;
+        for (int op = SLAK_TAIL_LN_FWD; op <= SLAK_TAIL_SR_BWD; ++op)
+            for (int sdt : {SLAK_F32, SLAK_BF16}) p.ok = p.ok && slak_block_tail_family(op, sdt, s.N, s.C, s.P, s.Cp) != SLAK_TAIL_FAMILY_NONE;
+    }
+    p.nt1 = slak_linear_nt_supported(s.M, s.C4, s.Cp, 1) != 0;      // pwconv1 + GELU in one streaming pass
+    p.nt2 = slak_linear_nt_supported(s.M, s.Cp, s.C4, 0) != 0;      // pwconv2
+    p.ntd1 = slak_linear_nt_supported(s.M, s.C4, s.Cp, 0) != 0;     // dz W2
+    p.ntd2 = slak_linear_nt_supported(s.M, s.Cp, s.C4, 0) != 0;     // dy1 W1
+    p.wg1 = slak_linear_wgrad_supported(s.M, s.C4, s.Cp) != 0;      // dW1 = dy1^T t
+    p.wg2 = slak_linear_wgrad_supported(s.M, s.Cp, s.C4) != 0;      // dW2 = dz^T a
     p.bwd1 = slak_dwconv2d_tri_backward_supported(dt, s.N, s.C, s.H, s.W, s.K) == 1;
-    p.gbwd = slak_linear_nt_gelu_bwd_supported(s.M, s.C4, s.C) == 1;
-    p.mlp1 = slak_linear_mlp_fwd_supported(s.M, s.C, s.C4) == 1;
-    p.gg1 = slak_linear_gemm_supported(s.M, s.C4, s.C, SLAK_EPI_GELU) == 1;    // stages 2-3: pwconv1 + GELU as one GEMM launch (round 5)
-    p.gg2 = slak_linear_gemm_supported(s.M, s.C4, s.C, SLAK_EPI_DGELU) == 1;   //             dz W2 + GELU' + pwconv1's bias gradient
+    p.gbwd = slak_linear_nt_gelu_bwd_supported(s.M, s.C4, s.Cp) == 1;
+    p.mlp1 = slak_linear_mlp_fwd_supported(s.M, s.Cp, s.C4) == 1;
+    p.gg1 = slak_linear_gemm_supported(s.M, s.C4, s.Cp, SLAK_EPI_GELU) == 1;    // stages 2-3: pwconv1 + GELU as one GEMM launch (round 5)
+    p.gg2 = slak_linear_gemm_supported(s.M, s.C4, s.Cp, SLAK_EPI_DGELU) == 1;   //             dz W2 + GELU' + pwconv1's bias gradient
     size_t ws = std::max(wtri, slak_bn3_workspace_bytes(s.N, s.C));
-    ws = std::max(ws, slak_block_tail_workspace_bytes(s.N, s.C, s.P));
+    ws = std::max(ws, slak_block_tail_workspace_bytes(s.N, s.Cp, s.P));
     ws = std::max(ws, slak_gelu_bwd_workspace_bytes(s.M, s.C4));
-    if (p.wg1) ws = std::max(ws, slak_linear_wgrad_workspace_bytes(s.M, s.C4, s.C));
-    if (p.wg2) ws = std::max(ws, slak_linear_wgrad_workspace_bytes(s.M, s.C, s.C4));
-    if (p.gbwd) ws = std::max(ws, slak_linear_nt_gelu_bwd_workspace_bytes(s.M, s.C4, s.C));
+    if (p.wg1) ws = std::max(ws, slak_linear_wgrad_workspace_bytes(s.M, s.C4, s.Cp));
+    if (p.wg2) ws = std::max(ws, slak_linear_wgrad_workspace_bytes(s.M, s.Cp, s.C4));
+    if (p.gbwd) ws = std::max(ws, slak_linear_nt_gelu_bwd_workspace_bytes(s.M, s.C4, s.Cp));
     // backward: the five calls whose final column sums are deferred into one launch keep their partial rows until then: a region each,
     // behind the scratch the other calls share -- [scale_residual][gelu'][LayerNorm][dW1][dW2]
     const auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-    const size_t tail = slak_block_tail_workspace_bytes(s.N, s.C, s.P);
+    const size_t tail = slak_block_tail_workspace_bytes(s.N, s.Cp, s.P);
     p.len[0] = tail; p.len[2] = tail;
-    p.len[1] = std::max(slak_gelu_bwd_workspace_bytes(s.M, s.C4), p.gbwd ? slak_linear_nt_gelu_bwd_workspace_bytes(s.M, s.C4, s.C) : (size_t)0);
-    if (p.gg2) p.len[1] = std::max(p.len[1], slak_linear_gemm_workspace_bytes(s.M, s.C4, s.C, SLAK_EPI_DGELU));
-    p.len[3] = p.wg1 ? slak_linear_wgrad_workspace_bytes(s.M, s.C4, s.C) : 0;
-    p.len[4] = p.wg2 ? slak_linear_wgrad_workspace_bytes(s.M, s.C, s.C4) : 0;
+    p.len[1] = std::max(slak_gelu_bwd_workspace_bytes(s.M, s.C4), p.gbwd ? slak_linear_nt_gelu_bwd_workspace_bytes(s.M, s.C4, s.Cp) : (size_t)0);
+    if (p.gg2) p.len[1] = std::max(p.len[1], slak_linear_gemm_workspace_bytes(s.M, s.C4, s.Cp, SLAK_EPI_DGELU));
+    p.len[3] = p.wg1 ? slak_linear_wgrad_workspace_bytes(s.M, s.C4, s.Cp) : 0;
+    p.len[4] = p.wg2 ? slak_linear_wgrad_workspace_bytes(s.M, s.Cp, s.C4) : 0;
     size_t o = up(ws);
     for (int k = 0; k < 5; ++k) { p.off[k] = o; p.len[k] = up(std::max<size_t>(p.len[k], 256)); o += p.len[k]; }
     p.ws = o;
@@ -162,7 +174,7 @@ const Plan& plan_of(const Shape& s) {
 Shape shape_of(const Tensor& x, const Tensor& wv, const Tensor& w1b) {
     Shape s;
     s.N = (int)x.size(0); s.C = (int)x.size(1); s.H = (int)x.size(2); s.W = (int)x.size(3); s.K = (int)wv.size(2);
-    s.P = s.H * s.W; s.M = s.N * s.P; s.C4 = (int)w1b.size(0);
+    s.P = s.H * s.W; s.M = s.N * s.P; s.C4 = (int)w1b.size(0); s.Cp = (int)w1b.size(1);
     return s;
 }
 
@@ -175,8 +187,11 @@ std::vector<Tensor> block_forward(const Tensor& x, const c10::optional<Tensor>& 
                                   const std::vector<Tensor>& bn_var, double bn_eps, double bn_momentum, bool update_running,
                                   const Tensor& lnw, const Tensor& lnb, double ln_eps, const Tensor& w1b, const Tensor& bb1b, const Tensor& w2b,
                                   const Tensor& bb2b, const Tensor& gamma, const c10::optional<Tensor>& sample_scale, bool emit_lowp,
-                                  const pybind11::object& exchange_obj /* None: single process; else see Exchange */) {
+                                  const pybind11::object& exchange_obj /* None: single process; else see Exchange */,
+                                  int64_t ldc /* row pitch of the NHWC tensors; != C: w1b .. bb2b are the zero-padded operands */) {
     Exchange exchange(exchange_obj);
+    TORCH_CHECK(w1b.dim() == 2 && w2b.dim() == 2 && ldc == w1b.size(1) && ldc == w2b.size(0) && w2b.size(1) == w1b.size(0) && bb1b.numel() == w1b.size(0) &&
+                bb2b.numel() == ldc, "the pointwise operands do not fit the pitch");
     TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 4, "x must be a contiguous (N,C,H,W) HIP tensor");
     TORCH_CHECK(bn_gamma.size() == 3 && bn_beta.size() == 3 && bn_mean.size() == 3 && bn_var.size() == 3, "three branch BatchNorms");
     const Shape s = shape_of(x, wv, w1b);
@@ -218,31 +233,35 @@ std::vector<Tensor> block_forward(const Tensor& x, const c10::optional<Tensor>& 
                                         s.N, s.C, s.P, st), "slak_bn3_forward_apply");
     }
     // permute + LayerNorm
-    Tensor t = at::empty({s.N, s.H, s.W, s.C}, x16.options());
+    const bool pitched = s.Cp != s.C;
+    Tensor t = at::empty({s.N, s.H, s.W, s.Cp}, x16.options());
     Tensor mean = at::empty({s.N, s.P}, stats.options()), rstd = at::empty({s.N, s.P}, stats.options());
+    if (pitched) check_rc(slak_ln_nchw_to_nhwc_forward_ld(sum.data_ptr(), fp(lnw), fp(lnb), t.data_ptr(), fpm(mean), fpm(rstd), s.N, s.C, s.P, (float)ln_eps, st, s.Cp),
+                          "slak_ln_nchw_to_nhwc_forward_ld");
+    else
     check_rc(slak_ln_nchw_to_nhwc_forward(sum.data_ptr(), fp(lnw), fp(lnb), t.data_ptr(), fpm(mean), fpm(rstd), s.N, s.C, s.P, (float)ln_eps, st),
              "slak_ln_nchw_to_nhwc_forward");
     // pwconv1 -> GELU -> pwconv2
     Tensor y1m, a, z;
     if (pl.mlp1) {                                                 // stage 1: pwconv1, GELU and pwconv2 in one pass
-        y1m = at::empty({s.N, s.H, s.W, s.C4}, x16.options()); a = at::empty_like(y1m); z = at::empty({s.N, s.H, s.W, s.C}, x16.options());
+        y1m = at::empty({s.N, s.H, s.W, s.C4}, x16.options()); a = at::empty_like(y1m); z = at::empty({s.N, s.H, s.W, s.Cp}, x16.options());
         check_rc(slak_linear_mlp_fwd(t.data_ptr(), w1b.data_ptr(), bb1b.data_ptr(), w2b.data_ptr(), bb2b.data_ptr(), y1m.data_ptr(), a.data_ptr(), z.data_ptr(),
-                                     s.M, s.C, s.C4, st), "slak_linear_mlp_fwd");
+                                     s.M, s.Cp, s.C4, st), "slak_linear_mlp_fwd");
     } else {
     if (pl.nt1) {
         y1m = at::empty({s.N, s.H, s.W, s.C4}, x16.options()); a = at::empty_like(y1m);
-        check_rc(slak_linear_nt(t.data_ptr(), w1b.data_ptr(), bb1b.data_ptr(), y1m.data_ptr(), a.data_ptr(), s.M, s.C4, s.C, st), "slak_linear_nt");
+        check_rc(slak_linear_nt(t.data_ptr(), w1b.data_ptr(), bb1b.data_ptr(), y1m.data_ptr(), a.data_ptr(), s.M, s.C4, s.Cp, st), "slak_linear_nt");
     } else if (pl.gg1) {                                           // stages 2-3: bias, rounding and GELU in the GEMM's epilogue
         y1m = at::empty({s.N, s.H, s.W, s.C4}, x16.options()); a = at::empty_like(y1m);
-        check_rc(slak_linear_gemm(t.data_ptr(), w1b.data_ptr(), bb1b.data_ptr(), y1m.data_ptr(), a.data_ptr(), nullptr, nullptr, s.M, s.C4, s.C, SLAK_EPI_GELU,
+        check_rc(slak_linear_gemm(t.data_ptr(), w1b.data_ptr(), bb1b.data_ptr(), y1m.data_ptr(), a.data_ptr(), nullptr, nullptr, s.M, s.C4, s.Cp, SLAK_EPI_GELU,
                                   nullptr, 0, st), "slak_linear_gemm");
     } else {
         y1m = at::linear(t, w1b, bb1b);
         a = at::gelu(y1m);
     }
     if (pl.nt2) {
-        z = at::empty({s.N, s.H, s.W, s.C}, x16.options());
-        check_rc(slak_linear_nt(a.data_ptr(), w2b.data_ptr(), bb2b.data_ptr(), z.data_ptr(), nullptr, s.M, s.C, s.C4, st), "slak_linear_nt");
+        z = at::empty({s.N, s.H, s.W, s.Cp}, x16.options());
+        check_rc(slak_linear_nt(a.data_ptr(), w2b.data_ptr(), bb2b.data_ptr(), z.data_ptr(), nullptr, s.M, s.Cp, s.C4, st), "slak_linear_nt");
     } else {
         z = at::linear(a, w2b, bb2b);
         if (z.scalar_type() != at::kBFloat16) z = z.to(at::kBFloat16);
@@ -253,6 +272,10 @@ std::vector<Tensor> block_forward(const Tensor& x, const c10::optional<Tensor>& 
     Tensor out = at::empty({s.N, s.C, s.H, s.W}, stats.options());
     Tensor out16 = emit_lowp ? at::empty({s.N, s.C, s.H, s.W}, x16.options()) : Tensor();
     const bool has_scale = sample_scale.has_value() && sample_scale->defined();
+    if (pitched) check_rc(slak_scale_residual_forward_ld(x.data_ptr(), x.scalar_type() == at::kFloat ? SLAK_F32 : SLAK_BF16, z.data_ptr(), fp(gamma),
+                                                         has_scale ? fp(*sample_scale) : nullptr, fpm(out), emit_lowp ? out16.data_ptr() : nullptr, s.N, s.C, s.P, st, s.Cp),
+                          "slak_scale_residual_forward_ld");
+    else
     check_rc(slak_scale_residual_forward(x.data_ptr(), x.scalar_type() == at::kFloat ? SLAK_F32 : SLAK_BF16, z.data_ptr(), fp(gamma),
                                          has_scale ? fp(*sample_scale) : nullptr, fpm(out), emit_lowp ? out16.data_ptr() : nullptr, s.N, s.C, s.P, st),
              "slak_scale_residual_forward");
@@ -313,11 +336,14 @@ std::vector<Tensor> block_backward(const Tensor& x16, const Tensor& wv, const Te
                                    const c10::optional<Tensor>& count_dev, const pybind11::object& exchange_obj, const pybind11::object& trace,
                                    const c10::optional<Tensor>& w1t_opt, const c10::optional<Tensor>& w2t_opt /* cached transposed bf16 weights, or None */,
                                    const c10::optional<Tensor>& w1p_opt /* W1^T in fragment-major order (slak_linear_nt_gelu_bwd_dt), or None */,
-                                   const std::vector<c10::optional<Tensor>>& grad_dst) {
+                                   const std::vector<c10::optional<Tensor>>& grad_dst, int64_t ldc /* as in block_forward */) {
     Exchange exchange(exchange_obj);
     const Shape s = shape_of(x16, wv, w1b);
+    TORCH_CHECK(ldc == s.Cp && z.size(-1) == ldc && t.size(-1) == ldc, "the saved tensors do not fit the pitch");
+    const bool pitched = s.Cp != s.C;
     TORCH_CHECK(grad_dst.empty() || grad_dst.size() == 16, "grad_dst: empty, or one entry (tensor or None) per parameter of the block");
     const GradDst gd{grad_dst.empty() ? nullptr : &grad_dst, (int)x16.get_device()};
+    const GradDst gdm = pitched ? GradDst{nullptr, (int)x16.get_device()} : gd;       // dW1, db1, dW2 of a pitched block come out padded and are cut at the end
     enum { G_WV, G_WH, G_WS, G_G1, G_B1, G_G2, G_B2, G_G3, G_B3, G_LNW, G_LNB, G_W1, G_BB1, G_W2, G_BB2, G_GAMMA };
     const Plan& pl = plan_of(s);
     TORCH_CHECK(pl.ok, "block_backward: the shape has no one-launch path (block_forward would have declined it)");
@@ -338,37 +364,42 @@ std::vector<Tensor> block_backward(const Tensor& x16, const Tensor& wv, const Te
     Tensor dsum = dout16.defined() ? at::empty_like(dout) : Tensor();
     Tensor dz = at::empty_like(z), dgamma = gd.take(G_GAMMA, {s.C}, f32), dzc = gd.take(G_BB2, {s.C}, f32);
     const bool has_scale = sample_scale.has_value() && sample_scale->defined();
+    if (pitched)                                                   // (a final reduction the library cannot defer runs at once: the same sums)
+    check_rc(slak_scale_residual_backward_ld(fp(dout), dout16.defined() ? dout16.data_ptr() : nullptr, dsum.defined() ? fpm(dsum) : nullptr, z.data_ptr(),
+                                             fp(gamma), has_scale ? fp(*sample_scale) : nullptr, dz.data_ptr(), fpm(dgamma), fpm(dzc), s.N, s.C, s.P,
+                                             region(0).p, region(0).n, st, s.Cp), "slak_scale_residual_backward_ld");
+    else
     check_rc(slak_scale_residual_backward(fp(dout), dout16.defined() ? dout16.data_ptr() : nullptr, dsum.defined() ? fpm(dsum) : nullptr, z.data_ptr(),
                                           fp(gamma), has_scale ? fp(*sample_scale) : nullptr, dz.data_ptr(), fpm(dgamma), fpm(dzc), s.N, s.C, s.P,
                                           region(0).p, region(0).n, st), "slak_scale_residual_backward");
     Tensor dshortcut = dsum.defined() ? dsum : dout;
     if (shortcut_bf16) dshortcut = dshortcut.to(at::kBFloat16);
     // the MLP's data path: dz -> dact -> (GELU') dy1 (+ pwconv1's bias gradient) -> dt
-    Tensor dz2 = dz.view({s.M, s.C});
+    Tensor dz2 = dz.view({s.M, s.Cp});
     const auto w2t_of = [&] { return (w2t_opt.has_value() && w2t_opt->defined()) ? *w2t_opt : w2b.t().contiguous(); };
     const auto w1t_of = [&] { return (w1t_opt.has_value() && w1t_opt->defined()) ? *w1t_opt : w1b.t().contiguous(); };
-    Tensor dact, dy1, dt_, db1 = gd.take(G_BB1, {s.C4}, f32);
-    if (pl.gbwd && w1p_opt.has_value() && w1p_opt->defined() && slak_linear_nt_gelu_bwd_dt_supported(s.M, s.C4, s.C) == 1) {
+    Tensor dact, dy1, dt_, db1 = gdm.take(G_BB1, {s.C4}, f32);
+    if (pl.gbwd && w1p_opt.has_value() && w1p_opt->defined() && slak_linear_nt_gelu_bwd_dt_supported(s.M, s.C4, s.Cp) == 1) {
         Tensor w2t = w2t_of();                                     // stage 1: the same with dt = dy1 W1 taken from the dy1 tiles while they are on chip
         dy1 = at::empty({s.M, s.C4}, x16.options());
-        dt_ = at::empty({s.M, s.C}, x16.options());
+        dt_ = at::empty({s.M, s.Cp}, x16.options());
         check_rc(slak_linear_nt_gelu_bwd_dt(dz2.data_ptr(), w2t.data_ptr(), y1m.data_ptr(), w1p_opt->data_ptr(), dy1.data_ptr(), dt_.data_ptr(), fpm(db1), s.M, s.C4,
-                                            s.C, region(1).p, region(1).n, st), "slak_linear_nt_gelu_bwd_dt");
+                                            s.Cp, region(1).p, region(1).n, st), "slak_linear_nt_gelu_bwd_dt");
     } else if (pl.gbwd) {                                          // stage 1: dz W2, GELU' and pwconv1's bias gradient in one pass
         Tensor w2t = w2t_of();
         dy1 = at::empty({s.M, s.C4}, x16.options());
-        check_rc(slak_linear_nt_gelu_bwd(dz2.data_ptr(), w2t.data_ptr(), y1m.data_ptr(), dy1.data_ptr(), fpm(db1), s.M, s.C4, s.C, region(1).p, region(1).n, st),
+        check_rc(slak_linear_nt_gelu_bwd(dz2.data_ptr(), w2t.data_ptr(), y1m.data_ptr(), dy1.data_ptr(), fpm(db1), s.M, s.C4, s.Cp, region(1).p, region(1).n, st),
                  "slak_linear_nt_gelu_bwd");
     } else if (pl.gg2) {                                           // stages 2-3: dz W2 with GELU' and pwconv1's bias gradient in the GEMM's epilogue
         Tensor w2t = w2t_of();
         dy1 = at::empty({s.M, s.C4}, x16.options());
-        check_rc(slak_linear_gemm(dz2.data_ptr(), w2t.data_ptr(), nullptr, dy1.data_ptr(), nullptr, y1m.data_ptr(), fpm(db1), s.M, s.C4, s.C, SLAK_EPI_DGELU,
+        check_rc(slak_linear_gemm(dz2.data_ptr(), w2t.data_ptr(), nullptr, dy1.data_ptr(), nullptr, y1m.data_ptr(), fpm(db1), s.M, s.C4, s.Cp, SLAK_EPI_DGELU,
                                   region(1).p, region(1).n, st), "slak_linear_gemm");
     } else {
     if (pl.ntd1) {
         Tensor w2t = w2t_of();
         dact = at::empty({s.M, s.C4}, x16.options());
-        check_rc(slak_linear_nt(dz2.data_ptr(), w2t.data_ptr(), nullptr, dact.data_ptr(), nullptr, s.M, s.C4, s.C, st), "slak_linear_nt");
+        check_rc(slak_linear_nt(dz2.data_ptr(), w2t.data_ptr(), nullptr, dact.data_ptr(), nullptr, s.M, s.C4, s.Cp, st), "slak_linear_nt");
     } else dact = at::mm(dz2, w2b);
     dy1 = at::empty_like(dact);
     check_rc(slak_gelu_backward_bias(dact.data_ptr(), y1m.data_ptr(), dy1.data_ptr(), fpm(db1), s.M, s.C4, region(1).p, region(1).n, st), "slak_gelu_backward_bias");
@@ -376,11 +407,15 @@ std::vector<Tensor> block_backward(const Tensor& x16, const Tensor& wv, const Te
     if (dt_.defined()) {
     } else if (pl.ntd2) {
         Tensor w1t = w1t_of();
-        dt_ = at::empty({s.M, s.C}, x16.options());
-        check_rc(slak_linear_nt(dy1.data_ptr(), w1t.data_ptr(), nullptr, dt_.data_ptr(), nullptr, s.M, s.C, s.C4, st), "slak_linear_nt");
+        dt_ = at::empty({s.M, s.Cp}, x16.options());
+        check_rc(slak_linear_nt(dy1.data_ptr(), w1t.data_ptr(), nullptr, dt_.data_ptr(), nullptr, s.M, s.Cp, s.C4, st), "slak_linear_nt");
     } else dt_ = at::mm(dy1, w1b);
     // permute + LayerNorm
     Tensor ds = at::empty_like(sum), dlnw = gd.take(G_LNW, {s.C}, f32), dlnb = gd.take(G_LNB, {s.C}, f32);
+    if (pitched)
+    check_rc(slak_ln_nchw_to_nhwc_backward_ld(dt_.data_ptr(), sum.data_ptr(), fp(lnw), fp(mean), fp(rstd), ds.data_ptr(), fpm(dlnw), fpm(dlnb), s.N, s.C, s.P,
+                                              region(2).p, region(2).n, st, s.Cp), "slak_ln_nchw_to_nhwc_backward_ld");
+    else
     check_rc(slak_ln_nchw_to_nhwc_backward(dt_.data_ptr(), sum.data_ptr(), fp(lnw), fp(mean), fp(rstd), ds.data_ptr(), fpm(dlnw), fpm(dlnb), s.N, s.C, s.P,
                                            region(2).p, region(2).n, st), "slak_ln_nchw_to_nhwc_backward");
     // SyncBatchNorm: the backward sums and their all-reduce go out FIRST (asynchronously); the weight gradients below do not depend on them
@@ -416,10 +451,27 @@ std::vector<Tensor> block_backward(const Tensor& x16, const Tensor& wv, const Te
     Side& sd = side_of(x16.get_device());
     const bool forked = sd.ok && pl.wg1 && pl.wg2 && hipEventRecord(sd.fork, (hipStream_t)st) == hipSuccess && hipStreamWaitEvent(sd.st, sd.fork, 0) == hipSuccess;
     void* wst = forked ? (void*)sd.st : st;
-    Tensor dw1 = wgrad(dy1, t.view({s.M, s.C}), s.M, s.C4, s.C, pl.wg1, region(3), wst, gd, G_W1);
-    Tensor dw2 = wgrad(dz2, a.view({s.M, s.C4}), s.M, s.C, s.C4, pl.wg2, region(4), wst, gd, G_W2);
-    struct Join { Side* sd; void* st; bool on; ~Join() { if (on && hipEventRecord(sd->join, sd->st) == hipSuccess) (void)hipStreamWaitEvent((hipStream_t)st, sd->join, 0); } } join{&sd, st, forked};
+    Tensor dw1 = wgrad(dy1, t.view({s.M, s.Cp}), s.M, s.C4, s.Cp, pl.wg1, region(3), wst, gdm, G_W1);
+    Tensor dw2 = wgrad(dz2, a.view({s.M, s.C4}), s.M, s.Cp, s.C4, pl.wg2, region(4), wst, gdm, G_W2);
+    struct Join { Side* sd; void* st; bool on;
+                  void now() { if (on && hipEventRecord(sd->join, sd->st) == hipSuccess) (void)hipStreamWaitEvent((hipStream_t)st, sd->join, 0); on = false; }
+                  ~Join() { now(); } } join{&sd, st, forked};
     check_rc(deferred.end(), "slak_defer_reductions_end");         // one launch: dgamma, db2 | db1 | dlnw, dlnb | dW1 | dW2
+    if (pitched) {
+        // dW1, db1, dW2 cut back to the parameters' shapes as contiguous fp32 (the pad rows and columns hold zeros) -- into the caller's tensor where one is
+        // usable.  Behind the deferred reductions, which finish them, and behind the side stream's join.
+        join.now();
+        const auto cut = [&](const Tensor& full, int slot, int64_t r, int64_t c) {
+            Tensor src = c > 0 ? full.narrow(0, 0, r).narrow(1, 0, c) : full.narrow(0, 0, r);
+            if (!gd.usable(slot, c > 0 ? r * c : r)) return src.contiguous();
+            Tensor d = c > 0 ? gd.take(slot, {r, c}, f32) : gd.take(slot, {r}, f32);
+            d.copy_(src);
+            return d;
+        };
+        dw1 = cut(dw1, G_W1, 4 * (int64_t)s.C, s.C);
+        db1 = cut(db1, G_BB1, 4 * (int64_t)s.C, 0);
+        dw2 = cut(dw2, G_W2, s.C, 4 * (int64_t)s.C);
+    }
     // branch BatchNorms
     if (exchange.none()) {
     check_rc(slak_bn3_backward_local_to(ds.data_ptr(), yv.data_ptr(), yh.data_ptr(), ys.data_ptr(), fp(bnstats), gam, fpm(bcoef), dgam3, dbet3,

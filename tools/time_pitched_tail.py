@@ -5,7 +5,8 @@ with C = ldc channels of the same N and P (the sibling moves at least as many by
     python tools/time_pitched_tail.py [--batch 128] [--reps 20] [--rounds 7]
 
 Device events around `reps` back-to-back launches, `rounds` rounds per entry point, pitched and sibling rounds alternating; one JSON line
-per (shape, op): the median round in us per launch and the spread (min, max) of both.
+per (shape, op): the median round in us per launch and the spread (min, max) of both, and beside each time the kernel family that
+slak_block_tail_family names for the call (tile / reg / chan / chan1).
 """
 import argparse
 import json
@@ -35,6 +36,10 @@ def main():
     dev = torch.device("cuda", 0)
     st = torch.cuda.current_stream(dev).cuda_stream
     N = a.batch
+    fam_op = {"ln_fwd": _lib.TAIL_LN_FWD, "ln_bwd": _lib.TAIL_LN_BWD, "sr_fwd": _lib.TAIL_SR_FWD, "sr_bwd": _lib.TAIL_SR_BWD}
+
+    def family(name, Cx, P, pitch):
+        return _lib.TAIL_FAMILY_NAMES[L.slak_block_tail_family(fam_op[name], _lib.SLAK_F32, N, Cx, P, pitch)]
 
     def timed(fn):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -84,6 +89,7 @@ def main():
             for _ in range(a.rounds):
                 tp.append(timed(pitched[name])); ts.append(timed(sibling[name]))
             print(json.dumps({"op": name, "N": N, "C": C, "P": P, "ldc": ldc,
+                              "pitched_family": family(name, C, P, ldc), "sibling_family": family(name, ldc, P, ldc),
                               "pitched_us": round(statistics.median(tp), 2), "pitched_min_max_us": [round(min(tp), 2), round(max(tp), 2)],
                               "sibling_C_eq_ldc_us": round(statistics.median(ts), 2), "sibling_min_max_us": [round(min(ts), 2), round(max(ts), 2)]}), flush=True)
         del po, so, pitched, sibling

@@ -1,10 +1,13 @@
-"""Step time of SLaK-T at a width factor (default 1.3: the width of every README recipe, C = 124 / 249 / 499 / 998), with bench.py's protocol:
+"""Step time of SLaK-T / -S / -B at a width factor (default 1.3: the width of every README recipe, C = 124 / 249 / 499 / 998 for SLaK-T and -S),
+with bench.py's protocol:
 
-    python tools/time_width.py [--width 1.3] [--batch 128] [--res 224] [--steps 20] [--warmup 5] [--prime 15]
+    python tools/time_width.py [--model tiny|small|base] [--width 1.3] [--batch 128] [--res 224] [--steps 20] [--warmup 5] [--prime 15]
 
 224 px, bf16 autocast, batch 128, MaskedAdamW, every fused path bench.py turns on; prime + warm-up steps, then K steps between two
 synchronisations.  Prints ONE JSON line: ms_per_step, host_enqueue_ms_per_step (three steps enqueued on a drained queue, the quietest of three
-rounds) and pitched_block_hits (block forwards that ran on pitched NHWC tensors: 0 on a tree without them, and at width 1.0).
+rounds), pitched_block_hits (block forwards that ran on pitched NHWC tensors: 0 on a tree without them, and at width 1.0) and
+pitched_runner_hits (those of them that the C++ block runner issued).  SLaK-B at width 1.3 (C = 166 / 332 / 665 / 1331) is outside the fused
+block path in stage 4 (C > 1024): its blocks there run the PyTorch ops.
 SLAK_PAD_EVEN=1 also pads the even widths 124 / 998 (block_ops.pad_even_widths).  bench.py itself has no width switch.
 """
 import argparse
@@ -23,6 +26,7 @@ import torch.nn as nn
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--model", choices=("tiny", "small", "base"), default="tiny")
     ap.add_argument("--width", type=float, default=1.3)
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--res", type=int, default=224)
@@ -48,7 +52,7 @@ def main():
     block_ops.cache_lowp_weights = True
     M.use_sync_bn = True
     torch.manual_seed(0)
-    model = M.create_model("SLaK_tiny", kernel_size=[51, 49, 47, 13, 5], Decom=True, bn=True, drop_path_rate=0.1, lowp_dwconv=True,
+    model = M.create_model("SLaK_" + a.model, kernel_size=[51, 49, 47, 13, 5], Decom=True, bn=True, drop_path_rate=0.1, lowp_dwconv=True,
                            width_factor=a.width).to(device)
     decay, no_decay = [], []
     for n, p in model.named_parameters():
@@ -72,12 +76,14 @@ def main():
         loss = step()
     torch.cuda.synchronize()
     hits0 = getattr(block_ops, "pitched_block_hits", 0)
+    rhits0 = getattr(block_ops, "pitched_runner_hits", 0)
     t0 = time.perf_counter()
     for _ in range(a.steps):
         loss = step()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     hits = getattr(block_ops, "pitched_block_hits", 0) - hits0
+    rhits = getattr(block_ops, "pitched_runner_hits", 0) - rhits0
     host = float("inf")
     for _ in range(3):
         h0 = time.perf_counter()
@@ -85,10 +91,12 @@ def main():
             step()
         host = min(host, (time.perf_counter() - h0) / 3)
         torch.cuda.synchronize()
-    dims = [int(d * a.width) for d in (96, 192, 384, 768)]
-    print(json.dumps({"workload": "SLaK-T 51x51, width_factor %g (C = %s), bs=%d, %dx%d, bf16, MaskedAdamW" % (a.width, dims, a.batch, a.res, a.res),
+    base_dims = (128, 256, 512, 1024) if a.model == "base" else (96, 192, 384, 768)
+    dims = [int(d * a.width) for d in base_dims]
+    print(json.dumps({"workload": "SLaK-%s 51x51, width_factor %g (C = %s), bs=%d, %dx%d, bf16, MaskedAdamW" % (a.model[0].upper(), a.width, dims, a.batch, a.res, a.res),
                       "ms_per_step": round(1e3 * elapsed / a.steps, 4), "host_enqueue_ms_per_step": round(1e3 * host, 3),
                       "pitched_block_hits": int(hits), "pitched_block_hits_per_step": hits / max(1, a.steps),
+                      "pitched_runner_hits_per_step": rhits / max(1, a.steps),
                       "pad_even_widths": bool(getattr(block_ops, "pad_even_widths", False)),
                       "nhwc_pitch": [block_ops.nhwc_pitch(c) if hasattr(block_ops, "nhwc_pitch") else None for c in dims],
                       "block_runner": bool(block_ops._runner() is not None), "steps": a.steps, "warmup": a.warmup, "prime": a.prime,
