@@ -538,6 +538,46 @@ int slak_ema_plan_create(const slak_ema_segment_t* segs_host, int nseg, slak_ema
 int slak_ema_update(slak_ema_plan_t* plan, double decay, void* stream);
 int slak_ema_plan_destroy(slak_ema_plan_t* plan);
 
+/* ---------------------------------------------------------------- the tail of the step: pooled LayerNorm head and the criterion
+ *
+ * slak_pool_ln_* = models/SLaK.py's `self.norm(x.mean([-2, -1]))` (the last line of forward_features): global average pool over the P = H * W
+ * pixels of every plane of x[N][C][P] (NCHW contiguous, fp32 or bf16; no alignment of a plane is assumed), then nn.LayerNorm over C.
+ * fp32 statistics: the plane sums are taken relative to the image's first element and divided by P, the variance over C is two-pass.
+ * Forward: ONE launch.  y[N][C] in y_dtype (fp32 or bf16); pooled[N][C] (the plane means), mean[N], rstd[N] fp32 are what the backward reads.
+ * Backward: dx[n][c][p] = dpool[n][c] / P for every pixel of a plane (x's dtype), dweight[C] / dbias[C] fp32 summed over the images in image
+ * order by a second launch (TWO launches).  dy in dy_dtype (fp32 or bf16).  Covers C <= 2048 and P <= 1024 with N * C * P < 2^31; anything
+ * else is SLAK_ERR_UNSUPPORTED, decided on the host before any launch (slak_pool_ln_supported: host code, no device needed). */
+int slak_pool_ln_supported(int x_dtype, int N, int C, int P);
+size_t slak_pool_ln_workspace_bytes(int N, int C, int P);            /* of slak_pool_ln_backward (the forward needs none) */
+int slak_pool_ln_forward(const void* x, int x_dtype, const float* weight, const float* bias, float eps, void* y, int y_dtype,
+                         float* pooled, float* mean, float* rstd, int N, int C, int P, void* stream);
+int slak_pool_ln_backward(const void* dy, int dy_dtype, const float* pooled, const float* weight, const float* mean, const float* rstd,
+                          void* dx, int x_dtype, float* dweight, float* dbias, int N, int C, int P,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
+/* slak_xent_* = the criterion main.py:398-403 picks: F.cross_entropy(logits, labels, label_smoothing = smoothing, ignore_index) with
+ * reduction 'mean' (nn.CrossEntropyLoss; smoothing > 0: timm1/loss/cross_entropy.py:20-26, LabelSmoothingCrossEntropy) when `labels` is
+ * given, sum_k -t_k log_softmax(x)_k averaged over the rows (timm1/loss/cross_entropy.py:34-36, SoftTargetCrossEntropy) when
+ * `soft_targets` is.  Exactly one of the two is non-NULL.  logits[N][K] fp32 / bf16 / fp16, row n at logits + n * row_stride elements (no
+ * alignment of a row is assumed); labels int64 [N]; soft_targets fp32 [N][K] contiguous.  Per row, in fp32, with m the row maximum:
+ *   lse = m + log sum_k exp(x_k - m)
+ *   hard label y:  loss_n = (1 - smoothing) (lse - x_y) + smoothing (lse - mean_k x_k);  d_k = g / count (p_k - (1 - smoothing) [k == y] - smoothing / K)
+ *   soft target t: loss_n = lse sum_k t_k - sum_k t_k x_k;                                 d_k = g / N (p_k sum_k t_k - t_k)
+ * A row whose label equals ignore_index gives loss 0, gradient 0 and is left out of count (torch's 'mean').  A label never forms an
+ * address: x_y is picked up by comparing k with y while the row is read, so a label outside [0, K) reads nothing (its row then has x_y = 0).
+ * Forward: ONE launch.  loss[1] = sum_n loss_n / count, lse[N], count[1] (fp32: the number of rows that count; N for soft targets).  The
+ * sum over the rows is taken in row order by the workgroup that finishes last (the arrival counters of the weight-gradient kernels): bitwise
+ * reproducible, no floating-point atomics.  Backward: ONE launch.  grad_out is a DEVICE pointer to one fp32 (no host read); dlogits[N][K]
+ * contiguous, in the logits' dtype.  Covers 1 <= K <= 32768, any N >= 1 with N * row_stride < 2^31. */
+int slak_xent_supported(int logits_dtype, int N, int K);
+size_t slak_xent_workspace_bytes(int N, int K);                      /* of slak_xent_forward (the backward needs none) */
+int slak_xent_forward(const void* logits, int logits_dtype, long long row_stride, const long long* labels, const float* soft_targets,
+                      float smoothing, long long ignore_index, float* loss, float* lse, float* count, int N, int K,
+                      void* workspace, size_t workspace_bytes, void* stream);
+int slak_xent_backward(const void* logits, int logits_dtype, long long row_stride, const long long* labels, const float* soft_targets,
+                       float smoothing, long long ignore_index, const float* lse, const float* count, const float* grad_out,
+                       void* dlogits, int N, int K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,3 +4,5 @@ hand-written HIP behind the reference's own operator surface.  See DESIGN.md / I
 from .depthwise_conv2d_implicit_gemm import DepthWiseConv2dImplicitGEMM  # noqa: F401
 
 __all__ = ["DepthWiseConv2dImplicitGEMM"]
+from .loss import CrossEntropyLoss, LabelSmoothingCrossEntropy, SoftTargetCrossEntropy  # noqa: E402,F401  (main.py:398-403's criteria)
+__all__ += ["CrossEntropyLoss", "LabelSmoothingCrossEntropy", "SoftTargetCrossEntropy"]

@@ -157,6 +157,14 @@ SIGNATURES = {
     "slak_scale_residual_backward_ld": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp, _i]),
     "slak_block_tail_family": (_i, [_i, _i, _i, _i, _i, _i]),      # (op, shortcut_dtype, N, C, P, ldc) -> TAIL_FAMILY_*; host only
     "slak_pad_cast_bf16_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "slak_pool_ln_supported": (_i, [_i, _i, _i, _i]),             # (x_dtype, N, C, P); host only
+    "slak_pool_ln_workspace_bytes": (_sz, [_i, _i, _i]),
+    "slak_pool_ln_forward": (_i, [_vp, _i, _vp, _vp, ctypes.c_float, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "slak_pool_ln_backward": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
+    "slak_xent_supported": (_i, [_i, _i, _i]),                    # (logits_dtype, N, K); host only
+    "slak_xent_workspace_bytes": (_sz, [_i, _i]),
+    "slak_xent_forward": (_i, [_vp, _i, ctypes.c_longlong, _vp, _vp, ctypes.c_float, ctypes.c_longlong, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
+    "slak_xent_backward": (_i, [_vp, _i, ctypes.c_longlong, _vp, _vp, ctypes.c_float, ctypes.c_longlong, _vp, _vp, _vp, _vp, _i, _i, _vp]),
 }
 # slak_block_tail_family: ops and answers (include/slak_hip.h)
 TAIL_LN_FWD, TAIL_LN_BWD, TAIL_SR_FWD, TAIL_SR_BWD = 0, 1, 2, 3

@@ -1705,3 +1705,62 @@ def fused_block(x, x_lowp, wv, wh, ws, bns, lnw, lnb, eps, w1, bb1, w2, bb2, gam
     cfg = {"bns": bns, "eps": eps, "emit_lowp": emit_lowp}
     return _BlockFn.apply(x, x_lowp, wv, wh, ws, bns[0].weight, bns[0].bias, bns[1].weight, bns[1].bias, bns[2].weight, bns[2].bias,
                           lnw, lnb, w1, bb1, w2, bb2, gamma, sample_scale, cfg)
+
+
+# ---- the head: global average pool + LayerNorm (models/SLaK.py: `self.norm(x.mean([-2, -1]))`, the last line of forward_features) ----
+head_hits = 0                 # forwards of pool_ln so far (tests, tools/time_width.py)
+
+
+def pool_ln_covers(x):
+    """slak_pool_ln_supported for a 4-D NCHW tensor (host code)."""
+    if x.dim() != 4 or x.dtype not in _SDT:
+        return False
+    N, C, H, W = x.shape
+    return N > 0 and bool(_lib.lib().slak_pool_ln_supported(_SDT[x.dtype], N, C, H * W))
+
+
+class _PoolLn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps, out_dtype):
+        global head_hits
+        _chk(x, "x"); _chk(weight, "weight", torch.float32); _chk(bias, "bias", torch.float32)
+        if x.dim() != 4 or x.dtype not in _SDT or out_dtype not in _SDT:
+            raise TypeError("x must be a 4-D float32 / bfloat16 tensor, out float32 or bfloat16")
+        N, C, H, W = x.shape
+        y = torch.empty((N, C), dtype=out_dtype, device=x.device)
+        pooled = torch.empty((N, C), dtype=torch.float32, device=x.device)
+        mean = torch.empty((N,), dtype=torch.float32, device=x.device)
+        rstd = torch.empty_like(mean)
+        with _on(x.device):
+            _lib.check(_lib.lib().slak_pool_ln_forward(x.data_ptr(), _SDT[x.dtype], weight.data_ptr(), bias.data_ptr(), float(eps), y.data_ptr(),
+                                                       _SDT[out_dtype], pooled.data_ptr(), mean.data_ptr(), rstd.data_ptr(), N, C, H * W,
+                                                       _stream(x.device)), "slak_pool_ln_forward")
+        ctx.save_for_backward(pooled, weight, mean, rstd)
+        ctx.x_shape, ctx.x_dtype = x.shape, x.dtype
+        head_hits += 1
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        pooled, weight, mean, rstd = ctx.saved_tensors
+        N, C, H, W = ctx.x_shape
+        g = g.contiguous()
+        if g.dtype not in _SDT:
+            g = g.float()
+        dx = torch.empty(ctx.x_shape, dtype=ctx.x_dtype, device=g.device)
+        dw = torch.empty_like(weight); db = torch.empty_like(weight)
+        L = _lib.lib()
+        ws, nb = _workspace(L.slak_pool_ln_workspace_bytes(N, C, H * W), g.device)
+        with _on(g.device):
+            _lib.check(L.slak_pool_ln_backward(g.data_ptr(), _SDT[g.dtype], pooled.data_ptr(), weight.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                               dx.data_ptr(), _SDT[ctx.x_dtype], dw.data_ptr(), db.data_ptr(), N, C, H * W,
+                                               ws.data_ptr() if ws is not None else None, nb, _stream(g.device)), "slak_pool_ln_backward")
+        return dx, dw, db, None, None
+
+
+def pool_ln(x, weight, bias, eps=1e-6):
+    """== F.layer_norm(x.mean([-2, -1]), (C,), weight, bias, eps) for x (N, C, H, W) float32 or bfloat16: one launch forward, two backward
+    (slak_pool_ln_*).  The result has the dtype the two torch ops give: float32 for float32 x and under autocast, bfloat16 for bfloat16 x outside
+    autocast.  No fallback: a shape slak_pool_ln_supported declines raises (callers ask pool_ln_covers first)."""
+    out_dtype = torch.float32 if (x.dtype == torch.float32 or torch.is_autocast_enabled()) else x.dtype
+    return _PoolLn.apply(x.contiguous(), weight, bias, eps, out_dtype)

@@ -463,6 +463,14 @@ class SLaK(nn.Module):
                     x = st(ds[1](y))
                 continue
             x = self.stages[i](ds(x))
+        norm = self.norm
+        if (self.fused_head and no_global_hooks and x.is_cuda and x.dim() == 4 and x.dtype in (torch.float32, torch.bfloat16)
+                and type(norm) is nn.LayerNorm and norm.elementwise_affine and norm.bias is not None and len(norm.normalized_shape) == 1
+                and norm.normalized_shape[0] == x.shape[1] and norm.weight.dtype == torch.float32 and norm.bias.dtype == torch.float32
+                and not (norm._forward_hooks or norm._forward_pre_hooks or norm._backward_hooks or norm._backward_pre_hooks)):
+            from . import block_ops                               # pool + LayerNorm as one launch (two backward) instead of the two torch ops
+            if block_ops.pool_ln_covers(x):
+                return block_ops.pool_ln(x, norm.weight, norm.bias, norm.eps)
         return self.norm(x.mean([-2, -1]))
 
     def forward(self, x):
@@ -472,6 +480,7 @@ class SLaK(nn.Module):
 SLaK.stem_lowp_handoff = True                # (with fused_stem) the stem LayerNorm hands the first block its bf16 input copy (block_ops.ln_channels_first_pair)
 SLaK.fused_stem = True                       # (with fused_downsample) the stem conv as patch matrix + library GEMMs (block_ops.stem_conv)
 SLaK.fused_downsample = False                # downsample layers as LN-to-patch-matrix kernel + library GEMMs (block_ops.downsample_ln_conv)
+SLaK.fused_head = False                      # global average pool + the final LayerNorm as one launch (block_ops.pool_ln); off: the two torch ops
 
 
 _VARIANTS = {

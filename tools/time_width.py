@@ -9,6 +9,8 @@ rounds), pitched_block_hits (block forwards that ran on pitched NHWC tensors: 0 
 pitched_runner_hits (those of them that the C++ block runner issued).  SLaK-B at width 1.3 (C = 166 / 332 / 665 / 1331) is outside the fused
 block path in stage 4 (C > 1024): its blocks there run the PyTorch ops.
 SLAK_PAD_EVEN=1 also pads the even widths 124 / 998 (block_ops.pad_even_widths).  bench.py itself has no width switch.
+--fused-head turns SLaK.fused_head on; --criterion label_smoothing | soft_target runs the criterion of slak_amd.loss (its HIP kernel) instead of
+torch's nn.CrossEntropyLoss(label_smoothing=0.1); head_hits_per_step / fused_hits_per_step count the calls the two kernels served.
 """
 import argparse
 import json
@@ -33,6 +35,9 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--prime", type=int, default=15)
+    ap.add_argument("--fused-head", action="store_true", help="SLaK.fused_head: pool + final LayerNorm as one launch (block_ops.pool_ln)")
+    ap.add_argument("--criterion", choices=("label_smoothing", "soft_target"), default=None,
+                    help="the criterion of slak_amd.loss on its HIP kernel (default: torch's nn.CrossEntropyLoss(label_smoothing=0.1))")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("tools/time_width.py needs an MI355X (no CPU fallback for the hot path)")
@@ -51,6 +56,8 @@ def main():
     M.Block.fused_block = True
     block_ops.cache_lowp_weights = True
     M.use_sync_bn = True
+    if a.fused_head:
+        M.SLaK.fused_head = True
     torch.manual_seed(0)
     model = M.create_model("SLaK_" + a.model, kernel_size=[51, 49, 47, 13, 5], Decom=True, bn=True, drop_path_rate=0.1, lowp_dwconv=True,
                            width_factor=a.width).to(device)
@@ -62,6 +69,17 @@ def main():
     g = torch.Generator(device=device).manual_seed(1234)
     samples = torch.randn(a.batch, 3, a.res, a.res, device=device, generator=g)
     targets = torch.randint(0, 1000, (a.batch,), device=device, generator=g)
+    if a.criterion is not None:
+        import slak_amd
+        if a.criterion == "label_smoothing":
+            criterion = slak_amd.LabelSmoothingCrossEntropy(0.1)
+        else:                                                    # a mixup-shaped target, built on the device once: two classes share 0.9, the floor is 0.1 / K
+            criterion = slak_amd.SoftTargetCrossEntropy()
+            hard = targets
+            targets = torch.full((a.batch, 1000), 0.1 / 1000, device=device)
+            targets[torch.arange(a.batch, device=device), hard] += 0.9 * 0.7
+            targets[torch.arange(a.batch, device=device), hard.flip(0)] += 0.9 * 0.3
+    from slak_amd import loss as slak_loss
 
     def step():
         with torch.autocast("cuda", dtype=torch.bfloat16):
@@ -77,6 +95,7 @@ def main():
     torch.cuda.synchronize()
     hits0 = getattr(block_ops, "pitched_block_hits", 0)
     rhits0 = getattr(block_ops, "pitched_runner_hits", 0)
+    head0, fused0 = block_ops.head_hits, slak_loss.fused_hits
     t0 = time.perf_counter()
     for _ in range(a.steps):
         loss = step()
@@ -84,6 +103,7 @@ def main():
     elapsed = time.perf_counter() - t0
     hits = getattr(block_ops, "pitched_block_hits", 0) - hits0
     rhits = getattr(block_ops, "pitched_runner_hits", 0) - rhits0
+    head_hits, fused_hits = block_ops.head_hits - head0, slak_loss.fused_hits - fused0
     host = float("inf")
     for _ in range(3):
         h0 = time.perf_counter()
@@ -97,6 +117,8 @@ def main():
                       "ms_per_step": round(1e3 * elapsed / a.steps, 4), "host_enqueue_ms_per_step": round(1e3 * host, 3),
                       "pitched_block_hits": int(hits), "pitched_block_hits_per_step": hits / max(1, a.steps),
                       "pitched_runner_hits_per_step": rhits / max(1, a.steps),
+                      "fused_head": bool(a.fused_head), "criterion": a.criterion or "torch", "head_hits_per_step": head_hits / max(1, a.steps),
+                      "fused_hits_per_step": fused_hits / max(1, a.steps),
                       "pad_even_widths": bool(getattr(block_ops, "pad_even_widths", False)),
                       "nhwc_pitch": [block_ops.nhwc_pitch(c) if hasattr(block_ops, "nhwc_pitch") else None for c in dims],
                       "block_runner": bool(block_ops._runner() is not None), "steps": a.steps, "warmup": a.warmup, "prime": a.prime,
