@@ -578,6 +578,47 @@ int slak_xent_backward(const void* logits, int logits_dtype, long long row_strid
                        float smoothing, long long ignore_index, const float* lse, const float* count, const float* grad_out,
                        void* dlogits, int N, int K, void* stream);
 
+/* ---------------------------------------------------------------- Mixup / CutMix of a batch
+ *
+ * What timm's Mixup (timm1/data/mixup.py:90-218; built at main.py:296-299, applied to every batch at engine.py:49-50) does on the device, one
+ * launch per pass.  The random numbers are drawn on the HOST, in the reference's order (slak_amd/mixup.py); these entries get finished
+ * per-image records.  Image n is always paired with image N-1-n, so N must be even.
+ *
+ * A record: what happens to one image, and the coefficients of its target row.
+ *   SLAK_MIXUP_NONE    the image stays as it is, bit for bit (lam == 1, mixing switched off, an element skipped under prob < 1)
+ *   SLAK_MIXUP_MIX     x_n = round(x_n a) + round(x_j b): two fp32 multiplies, each rounded, then an add -- torch's op sequence, not an fma
+ *   SLAK_MIXUP_CUTMIX  x_n[:, yl:yh, xl:xh] = x_j[:, yl:yh, xl:xh]: the partner's BITS; nothing outside the box is read into or written in image n
+ * with j = N-1-n and x_j the partner's ORIGINAL values.  a, b are computed on the host exactly as the reference computes lam and 1 - lam and
+ * rounded to fp32 once; for every kind they are the target coefficients as well.  The records arrive one of two ways (exactly one non-NULL):
+ * `shared_host`, ONE record in host memory that every image shares ('batch' mode: it travels as a kernel argument, nothing is copied to the
+ * device), or `table_dev`, a DEVICE array of N records ('pair' / 'elem' modes).  A shared record is checked on the host (unknown kind, box
+ * outside the image: SLAK_ERR_INVALID_ARG); a table's boxes are clipped to the image by the kernel and an unknown kind there means NONE.
+ *
+ * slak_mixup_images = timm1/data/mixup.py:159-207 (_mix_elem, _mix_pair, _mix_batch): x[N][C][H][W] fp32, NCHW contiguous, mixed IN PLACE
+ * without a copy of the batch -- the thread that owns an offset of image n owns the same offset of image N-1-n, loads both, then stores both.
+ * No alignment of an image or of a box row is assumed.  ONE launch (none when a shared record leaves every image as it is).
+ * Covers fp32, even 2 <= N <= 131070, C H W <= 2^28; anything else is SLAK_ERR_UNSUPPORTED, decided on the host before any launch.
+ *
+ * slak_mixup_targets = timm1/data/mixup.py:17-27 (one_hot, mixup_target): labels int64 [N] -> out fp32 [N][K] contiguous,
+ *   out[n][k] = round(v(y_n, k) a_n) + round(v(y_{N-1-n}, k) b_n),   v(y, k) = on_value where k == y, off_value elsewhere
+ * (the caller passes off = smoothing / K and on = 1 - smoothing + off, evaluated in double and rounded to fp32 once, as torch.full / scatter_
+ * do).  ONE launch.  A label never forms an address: it is compared with the column index, so a label outside [0, K) matches no column and
+ * its row holds off-values only -- torch's scatter_ raises a device-side assertion there instead.  Covers even N >= 2, K >= 1, N K <= 2^30. */
+#define SLAK_MIXUP_NONE 0
+#define SLAK_MIXUP_MIX 1
+#define SLAK_MIXUP_CUTMIX 2
+typedef struct {
+    int kind;                /* SLAK_MIXUP_*                                                   */
+    float a, b;              /* coefficient of the image's own values / label, of its partner's */
+    int yl, yh, xl, xh;      /* the CutMix box: rows [yl, yh), columns [xl, xh)                */
+} slak_mixup_record_t;
+int slak_mixup_images_supported(int x_dtype, int N, int C, int H, int W);
+int slak_mixup_images(void* x, int x_dtype, const slak_mixup_record_t* shared_host, const slak_mixup_record_t* table_dev,
+                      int N, int C, int H, int W, void* stream);
+int slak_mixup_targets_supported(int N, int K);
+int slak_mixup_targets(const long long* labels, const slak_mixup_record_t* shared_host, const slak_mixup_record_t* table_dev,
+                       float on_value, float off_value, float* out, int N, int K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,3 +6,5 @@ from .depthwise_conv2d_implicit_gemm import DepthWiseConv2dImplicitGEMM  # noqa:
 __all__ = ["DepthWiseConv2dImplicitGEMM"]
 from .loss import CrossEntropyLoss, LabelSmoothingCrossEntropy, SoftTargetCrossEntropy  # noqa: E402,F401  (main.py:398-403's criteria)
 __all__ += ["CrossEntropyLoss", "LabelSmoothingCrossEntropy", "SoftTargetCrossEntropy"]
+from .mixup import Mixup  # noqa: E402,F401  (main.py:21, 296-299's mixup_fn)
+__all__ += ["Mixup"]

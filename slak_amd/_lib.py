@@ -45,6 +45,11 @@ class EmaSegment(ctypes.Structure):
                 ("dtype", ctypes.c_int)]
 
 
+class MixupRecord(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int), ("a", ctypes.c_float), ("b", ctypes.c_float),
+                ("yl", ctypes.c_int), ("yh", ctypes.c_int), ("xl", ctypes.c_int), ("xh", ctypes.c_int)]
+
+
 # name -> (restype, argtypes): every symbol include/slak_hip.h declares (tests/test_boundary.py checks this)
 _vp, _i, _sz, _d = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_double
 _CONV = [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]
@@ -165,7 +170,12 @@ SIGNATURES = {
     "slak_xent_workspace_bytes": (_sz, [_i, _i]),
     "slak_xent_forward": (_i, [_vp, _i, ctypes.c_longlong, _vp, _vp, ctypes.c_float, ctypes.c_longlong, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
     "slak_xent_backward": (_i, [_vp, _i, ctypes.c_longlong, _vp, _vp, ctypes.c_float, ctypes.c_longlong, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "slak_mixup_images_supported": (_i, [_i, _i, _i, _i, _i]),    # (x_dtype, N, C, H, W); host only
+    "slak_mixup_images": (_i, [_vp, _i, ctypes.POINTER(MixupRecord), _vp, _i, _i, _i, _i, _vp]),      # (x, dtype, shared record on the host | NULL, device table | NULL, ...)
+    "slak_mixup_targets_supported": (_i, [_i, _i]),               # (N, K); host only
+    "slak_mixup_targets": (_i, [_vp, ctypes.POINTER(MixupRecord), _vp, ctypes.c_float, ctypes.c_float, _vp, _i, _i, _vp]),
 }
+MIXUP_NONE, MIXUP_MIX, MIXUP_CUTMIX = 0, 1, 2                      # slak_mixup_record_t.kind
 # slak_block_tail_family: ops and answers (include/slak_hip.h)
 TAIL_LN_FWD, TAIL_LN_BWD, TAIL_SR_FWD, TAIL_SR_BWD = 0, 1, 2, 3
 TAIL_FAMILY_NONE, TAIL_FAMILY_TILE, TAIL_FAMILY_REG, TAIL_FAMILY_CHAN, TAIL_FAMILY_CHAN1 = 0, 1, 2, 3, 4

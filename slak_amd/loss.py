@@ -59,24 +59,25 @@ class _Xent(torch.autograd.Function):
         soft = target.is_floating_point()
         target = target.to(torch.float32).contiguous() if soft else target.contiguous()
         dev = logits.device
-        out = torch.empty(2, dtype=torch.float32, device=dev)    # loss, count
+        loss = torch.empty((), dtype=torch.float32, device=dev)  # a tensor of its own: engine.py:79 divides the loss in place, which autograd refuses on a view
+        count = torch.empty(1, dtype=torch.float32, device=dev)
         lse = torch.empty(N, dtype=torch.float32, device=dev)
         L = _lib.lib()
         ws, nb = _workspace(L.slak_xent_workspace_bytes(N, K), dev)
         with _on(dev):
             _lib.check(L.slak_xent_forward(logits.data_ptr(), _DT[logits.dtype], logits.stride(0), None if soft else target.data_ptr(),
                                            target.data_ptr() if soft else None, float(label_smoothing), int(ignore_index),
-                                           out.data_ptr(), lse.data_ptr(), out.data_ptr() + 4, N, K,
+                                           loss.data_ptr(), lse.data_ptr(), count.data_ptr(), N, K,
                                            ws.data_ptr() if ws is not None else None, nb, _stream(dev)), "slak_xent_forward")
-        ctx.save_for_backward(logits, target, lse, out)
+        ctx.save_for_backward(logits, target, lse, count)
         ctx.args = (soft, float(label_smoothing), int(ignore_index))
         fused_hits += 1
-        return out[0]
+        return loss
 
     @staticmethod
     def backward(ctx, g):
         from .ops import _stream, _on
-        logits, target, lse, out = ctx.saved_tensors
+        logits, target, lse, count = ctx.saved_tensors
         soft, smoothing, ignore_index = ctx.args
         N, K = logits.shape
         dev = logits.device
@@ -85,7 +86,7 @@ class _Xent(torch.autograd.Function):
         with _on(dev):
             _lib.check(_lib.lib().slak_xent_backward(logits.data_ptr(), _DT[logits.dtype], logits.stride(0), None if soft else target.data_ptr(),
                                                      target.data_ptr() if soft else None, smoothing, ignore_index, lse.data_ptr(),
-                                                     out.data_ptr() + 4, g.data_ptr(), d.data_ptr(), N, K, _stream(dev)), "slak_xent_backward")
+                                                     count.data_ptr(), g.data_ptr(), d.data_ptr(), N, K, _stream(dev)), "slak_xent_backward")
         return d, None, None, None
 
 

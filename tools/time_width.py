@@ -11,6 +11,8 @@ block path in stage 4 (C > 1024): its blocks there run the PyTorch ops.
 SLAK_PAD_EVEN=1 also pads the even widths 124 / 998 (block_ops.pad_even_widths).  bench.py itself has no width switch.
 --fused-head turns SLaK.fused_head on; --criterion label_smoothing | soft_target runs the criterion of slak_amd.loss (its HIP kernel) instead of
 torch's nn.CrossEntropyLoss(label_smoothing=0.1); head_hits_per_step / fused_hits_per_step count the calls the two kernels served.
+--mixup (with --criterion soft_target) runs slak_amd.mixup.Mixup with the recipes' setting (mixup 0.8, cutmix 1.0, smoothing 0.1, 'batch' mode) on the
+batch and the hard labels in every step, as engine.py:49-50 does, and adds "mixup" / "mixup_hits_per_step" to the line; without the flag nothing changes.
 """
 import argparse
 import json
@@ -38,7 +40,10 @@ def main():
     ap.add_argument("--fused-head", action="store_true", help="SLaK.fused_head: pool + final LayerNorm as one launch (block_ops.pool_ln)")
     ap.add_argument("--criterion", choices=("label_smoothing", "soft_target"), default=None,
                     help="the criterion of slak_amd.loss on its HIP kernel (default: torch's nn.CrossEntropyLoss(label_smoothing=0.1))")
+    ap.add_argument("--mixup", action="store_true", help="slak_amd.mixup.Mixup on every batch (needs --criterion soft_target)")
     a = ap.parse_args()
+    if a.mixup and a.criterion != "soft_target":
+        ap.error("--mixup needs --criterion soft_target (main.py:397-399)")
     if not torch.cuda.is_available():
         sys.exit("tools/time_width.py needs an MI355X (no CPU fallback for the hot path)")
     device = torch.device("cuda", 0)
@@ -80,10 +85,17 @@ def main():
             targets[torch.arange(a.batch, device=device), hard] += 0.9 * 0.7
             targets[torch.arange(a.batch, device=device), hard.flip(0)] += 0.9 * 0.3
     from slak_amd import loss as slak_loss
+    mixup_fn = None
+    if a.mixup:
+        import numpy as np
+        from slak_amd import mixup as slak_mixup
+        np.random.seed(0)
+        mixup_fn = slak_mixup.Mixup(mixup_alpha=0.8, cutmix_alpha=1.0, label_smoothing=0.1, num_classes=1000)
 
     def step():
+        x, t = (samples, targets) if mixup_fn is None else mixup_fn(samples, hard)
         with torch.autocast("cuda", dtype=torch.bfloat16):
-            loss = criterion(model(samples), targets)
+            loss = criterion(model(x), t)
         loss.backward()
         opt.step()
         opt.zero_grad(set_to_none=True)
@@ -96,6 +108,7 @@ def main():
     hits0 = getattr(block_ops, "pitched_block_hits", 0)
     rhits0 = getattr(block_ops, "pitched_runner_hits", 0)
     head0, fused0 = block_ops.head_hits, slak_loss.fused_hits
+    mix0 = slak_mixup.fused_hits if a.mixup else 0
     t0 = time.perf_counter()
     for _ in range(a.steps):
         loss = step()
@@ -104,6 +117,7 @@ def main():
     hits = getattr(block_ops, "pitched_block_hits", 0) - hits0
     rhits = getattr(block_ops, "pitched_runner_hits", 0) - rhits0
     head_hits, fused_hits = block_ops.head_hits - head0, slak_loss.fused_hits - fused0
+    extra = {"mixup": True, "mixup_hits_per_step": (slak_mixup.fused_hits - mix0) / max(1, a.steps)} if a.mixup else {}
     host = float("inf")
     for _ in range(3):
         h0 = time.perf_counter()
@@ -122,7 +136,7 @@ def main():
                       "pad_even_widths": bool(getattr(block_ops, "pad_even_widths", False)),
                       "nhwc_pitch": [block_ops.nhwc_pitch(c) if hasattr(block_ops, "nhwc_pitch") else None for c in dims],
                       "block_runner": bool(block_ops._runner() is not None), "steps": a.steps, "warmup": a.warmup, "prime": a.prime,
-                      "final_loss": float(loss.item()), "gpu": torch.cuda.get_device_name(0)}), flush=True)
+                      "final_loss": float(loss.item()), "gpu": torch.cuda.get_device_name(0), **extra}), flush=True)
 
 
 if __name__ == "__main__":
