@@ -218,7 +218,8 @@ int slak_dwconv2d_pair_backward_filter(const void* dy_v, const void* dy_s, const
  * The layout / normalisation / residual steps around the two pointwise GEMMs of a SLaK block
  * (models/SLaK.py:153-166: permute -> LayerNorm -> [pwconv1, GELU, pwconv2] -> gamma -> permute -> shortcut + drop_path),
  * one HBM-bound kernel per arrow and direction.  Activations bf16, statistics / residual stream / parameters fp32.
- * P = H*W pixels per image; x, dx, shortcut, out are NCHW; y, g, z, dz are NHWC (N,H,W,C) contiguous; C even, <= 1024. */
+ * P = H*W pixels per image; x, dx, shortcut, out are NCHW; y, g, z, dz are NHWC (N,H,W,C) contiguous; C even, <= 1024.
+ * These four functions are the `_ld` ones below called with ldc = C. */
 size_t slak_block_tail_workspace_bytes(int N, int C, int P);
 
 /* y[n,p,:] = LayerNorm_C(x[n,:,p]) * weight + bias   (F.layer_norm over the last dim of x.permute(0,2,3,1): models/SLaK.py:156-157, :253-255) */
@@ -241,14 +242,14 @@ int slak_scale_residual_backward(const float* dout, const void* dout_bf16, float
                                  void* workspace, size_t workspace_bytes, void* stream);
 
 /* The same four ops with a row pitch on the NHWC side (`--width_factor 1.3`: C = 124 / 249 / 499 / 998).  The NCHW tensors (x, dx, shortcut,
- * out, dout) keep their logical C; y, g, z, dz are (N,H,W,ldc) contiguous, i.e. rows of ldc >= C elements.  1 <= C <= 1024 of ANY parity,
- * ldc % 8 == 0, ldc <= 1024, else SLAK_ERR_UNSUPPORTED; workspace >= slak_block_tail_workspace_bytes(N, ldc, P).  Arguments as the plain entry
- * points, ldc last.
+ * out, dout) keep their logical C; y, g, z, dz are (N,H,W,ldc) contiguous, i.e. rows of ldc >= C elements.  One argument rule, which
+ * slak_block_tail_family shares: 1 <= C <= ldc <= 1024 and N * ldc * P < 2^31; ldc == C needs an even C, ldc > C (C of ANY parity) needs
+ * ldc % 8 == 0; else SLAK_ERR_UNSUPPORTED.  workspace >= slak_block_tail_workspace_bytes(N, ldc, P).  Arguments as the plain entry points, ldc last.
  *   - the LayerNorm statistics and every 1/C factor use the logical C; columns c >= C never enter a sum;
  *   - columns c >= C of y and of dz are WRITTEN, as +0.0, on every call (the next GEMM reads whole rows);
  *   - columns c >= C of g and z are never used: they may hold anything, NaN included;
  *   - weight, bias, gamma, dweight, dbias, dgamma, dz_colsum are [C].
- * ldc == C (then C % 8 == 0) forwards to the plain entry point: the same bits.
+ * ldc == C is the plain call: the same checks, launches and bits.
  * Kernels: a pitched call runs the small-plane families of the plain entry points (H*W <= 256: a wave per image and group of 24-64 channels, one
  * pixel per lane on odd planes) exactly where the plain call on C = ldc runs them -- the channel groups tile the pitch, a group's live channel count
  * is a wave-uniform bound, a group of pad columns only writes its +0 --, plus, for the two LayerNorm ops on odd planes, 64 channels per wave where
@@ -266,7 +267,7 @@ int slak_scale_residual_backward_ld(const float* dout, const void* dout_bf16, fl
                                     void* workspace, size_t workspace_bytes, void* stream, int ldc);
 
 /* Which kernel family the block-tail entry points run for `op` on (N, C, P) with NHWC rows of ldc elements; ldc == C asks for the plain entry
- * point's choice.  Pure host code, callable without a device; the eight entry points choose their kernel through this very function, so the answer
+ * point's choice.  Pure host code, callable without a device; the four ops choose their kernel through this very function, so the answer
  * IS the launch.  NONE: the entry point would not launch (invalid or unsupported arguments; shortcut_dtype matters to SLAK_TAIL_SR_FWD only).
  * TILE: LDS-tile kernels; REG: pixel-pair register-tile kernels; CHAN / CHAN1: the small-plane families, even / odd H*W. */
 enum { SLAK_TAIL_LN_FWD = 0, SLAK_TAIL_LN_BWD = 1, SLAK_TAIL_SR_FWD = 2, SLAK_TAIL_SR_BWD = 3 };

@@ -44,22 +44,14 @@ def _ln_fwd_impl(x, weight, bias, eps, ldc=None):
     """ldc: row pitch of y (None / C: the plain op).  Pitched: y is (N,H,W,ldc) with exact zeros in the columns c >= C."""
     _chk(x, "x", torch.bfloat16); _chk(weight, "weight", torch.float32); _chk(bias, "bias", torch.float32)
     N, C, H, W = x.shape
-    if ldc is not None and ldc != C:
-        y = torch.empty((N, H, W, ldc), dtype=torch.bfloat16, device=x.device)
-        mean = torch.empty((N, H * W), dtype=torch.float32, device=x.device)
-        rstd = torch.empty_like(mean)
-        with _on(x.device):
-            _lib.check(_lib.lib().slak_ln_nchw_to_nhwc_forward_ld(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), y.data_ptr(), mean.data_ptr(),
-                                                                  rstd.data_ptr(), N, C, H * W, float(eps), _stream(x.device), int(ldc)),
-                       "slak_ln_nchw_to_nhwc_forward_ld")
-        return y, mean, rstd
-    y = torch.empty((N, H, W, C), dtype=torch.bfloat16, device=x.device)
+    ldc = C if ldc is None else int(ldc)
+    y = torch.empty((N, H, W, ldc), dtype=torch.bfloat16, device=x.device)
     mean = torch.empty((N, H * W), dtype=torch.float32, device=x.device)
     rstd = torch.empty_like(mean)
-    L = _lib.lib()
     with _on(x.device):
-        _lib.check(L.slak_ln_nchw_to_nhwc_forward(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), y.data_ptr(), mean.data_ptr(),
-                                                  rstd.data_ptr(), N, C, H * W, float(eps), _stream(x.device)), "slak_ln_nchw_to_nhwc_forward")
+        _lib.check(_lib.lib().slak_ln_nchw_to_nhwc_forward_ld(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), y.data_ptr(), mean.data_ptr(),
+                                                              rstd.data_ptr(), N, C, H * W, float(eps), _stream(x.device), ldc),
+                   "slak_ln_nchw_to_nhwc_forward_ld")
     return y, mean, rstd
 
 
@@ -81,21 +73,13 @@ def _ln_bwd_impl(g, x, weight, mean, rstd):
         g = g.to(torch.bfloat16)
     dx = torch.empty_like(x)
     dw = torch.empty_like(weight); db = torch.empty_like(weight)
-    L = _lib.lib()
-    ldc = g.shape[-1]
-    if ldc != C:                                       # pitched gradient (N,H,W,ldc): its columns c >= C are never read
-        ws, nb = _workspace(_tail_ws_bytes(N, ldc, H * W), x.device)
-        with _on(x.device):
-            _lib.check(L.slak_ln_nchw_to_nhwc_backward_ld(g.data_ptr(), x.data_ptr(), weight.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                                          dx.data_ptr(), dw.data_ptr(), db.data_ptr(), N, C, H * W,
-                                                          ws.data_ptr() if ws is not None else None, nb, _stream(x.device), ldc),
-                       "slak_ln_nchw_to_nhwc_backward_ld")
-        return dx, dw, db
-    ws, nb = _workspace(_tail_ws_bytes(N, C, H * W), x.device)
+    ldc = g.shape[-1]                                  # (N,H,W,ldc): the columns c >= C of a pitched gradient are never read
+    ws, nb = _workspace(_tail_ws_bytes(N, ldc, H * W), x.device)
     with _on(x.device):
-        _lib.check(L.slak_ln_nchw_to_nhwc_backward(g.data_ptr(), x.data_ptr(), weight.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                                   dx.data_ptr(), dw.data_ptr(), db.data_ptr(), N, C, H * W,
-                                                   ws.data_ptr() if ws is not None else None, nb, _stream(x.device)), "slak_ln_nchw_to_nhwc_backward")
+        _lib.check(_lib.lib().slak_ln_nchw_to_nhwc_backward_ld(g.data_ptr(), x.data_ptr(), weight.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                                               dx.data_ptr(), dw.data_ptr(), db.data_ptr(), N, C, H * W,
+                                                               ws.data_ptr() if ws is not None else None, nb, _stream(x.device), ldc),
+                   "slak_ln_nchw_to_nhwc_backward_ld")
     return dx, dw, db
 
 
@@ -124,19 +108,11 @@ def _scale_residual_fwd(shortcut, z, gamma, sample_scale, emit_lowp):
         raise TypeError("shortcut must be float32 or bfloat16")
     out = torch.empty((N, C, H, W), dtype=torch.float32, device=z.device)
     out16 = torch.empty((N, C, H, W), dtype=torch.bfloat16, device=z.device) if emit_lowp else None
-    L = _lib.lib()
-    if ldc != C:                                       # pitched z: its columns c >= C are never read
-        with _on(z.device):
-            _lib.check(L.slak_scale_residual_forward_ld(shortcut.data_ptr(), sdt, z.data_ptr(), gamma.data_ptr(),
-                                                        sample_scale.data_ptr() if sample_scale is not None else None,
-                                                        out.data_ptr(), out16.data_ptr() if emit_lowp else None,
-                                                        N, C, H * W, _stream(z.device), ldc), "slak_scale_residual_forward_ld")
-        return out, out16
-    with _on(z.device):
-        _lib.check(L.slak_scale_residual_forward(shortcut.data_ptr(), sdt, z.data_ptr(), gamma.data_ptr(),
-                                                 sample_scale.data_ptr() if sample_scale is not None else None,
-                                                 out.data_ptr(), out16.data_ptr() if emit_lowp else None,
-                                                 N, C, H * W, _stream(z.device)), "slak_scale_residual_forward")
+    with _on(z.device):                                # (the columns c >= C of a pitched z are never read)
+        _lib.check(_lib.lib().slak_scale_residual_forward_ld(shortcut.data_ptr(), sdt, z.data_ptr(), gamma.data_ptr(),
+                                                             sample_scale.data_ptr() if sample_scale is not None else None,
+                                                             out.data_ptr(), out16.data_ptr() if emit_lowp else None,
+                                                             N, C, H * W, _stream(z.device), ldc), "slak_scale_residual_forward_ld")
     return out, out16
 
 
@@ -157,26 +133,14 @@ def _scale_residual_bwd(z, gamma, sample_scale, shortcut_dtype, dout, dout16):
     dz = torch.empty_like(z)
     dgamma = torch.empty_like(gamma)
     dzc = torch.empty_like(gamma)
-    L = _lib.lib()
-    if ldc != C:
-        ws, nb = _workspace(_tail_ws_bytes(N, ldc, H * W), z.device)
-        with _on(z.device):
-            _lib.check(L.slak_scale_residual_backward_ld(dout.data_ptr(), dout16.data_ptr() if dout16 is not None else None,
-                                                         dsum.data_ptr() if dsum is not None else None, z.data_ptr(), gamma.data_ptr(),
-                                                         sample_scale.data_ptr() if sample_scale is not None else None,
-                                                         dz.data_ptr(), dgamma.data_ptr(), dzc.data_ptr(), N, C, H * W,
-                                                         ws.data_ptr() if ws is not None else None, nb, _stream(z.device), ldc),
-                       "slak_scale_residual_backward_ld")
-        dsc = dsum if dsum is not None else dout
-        return (dsc if shortcut_dtype == torch.float32 else dsc.to(shortcut_dtype)), dz, dgamma, dzc
-    ws, nb = _workspace(L.slak_block_tail_workspace_bytes(N, C, H * W), z.device)
+    ws, nb = _workspace(_tail_ws_bytes(N, ldc, H * W), z.device)
     with _on(z.device):
-        _lib.check(L.slak_scale_residual_backward(dout.data_ptr(), dout16.data_ptr() if dout16 is not None else None,
-                                                  dsum.data_ptr() if dsum is not None else None, z.data_ptr(), gamma.data_ptr(),
-                                                  sample_scale.data_ptr() if sample_scale is not None else None,
-                                                  dz.data_ptr(), dgamma.data_ptr(), dzc.data_ptr(), N, C, H * W,
-                                                  ws.data_ptr() if ws is not None else None, nb, _stream(z.device)),
-                   "slak_scale_residual_backward")
+        _lib.check(_lib.lib().slak_scale_residual_backward_ld(dout.data_ptr(), dout16.data_ptr() if dout16 is not None else None,
+                                                              dsum.data_ptr() if dsum is not None else None, z.data_ptr(), gamma.data_ptr(),
+                                                              sample_scale.data_ptr() if sample_scale is not None else None,
+                                                              dz.data_ptr(), dgamma.data_ptr(), dzc.data_ptr(), N, C, H * W,
+                                                              ws.data_ptr() if ws is not None else None, nb, _stream(z.device), ldc),
+                   "slak_scale_residual_backward_ld")
     dsc = dsum if dsum is not None else dout
     dshortcut = dsc if shortcut_dtype == torch.float32 else dsc.to(shortcut_dtype)
     return dshortcut, dz, dgamma, dzc

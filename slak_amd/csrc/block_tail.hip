@@ -1258,26 +1258,20 @@ size_t slak_block_tail_workspace_bytes(int N, int C, int P) {
 }
 
 static bool tail_use_reg() { static const bool v = slak_env_flag("SLAK_TAIL_REG", true); return v; }   // SLAK_TAIL_REG=0 keeps the LDS-tile kernels (A/B testing)
-static int tail_args_ok(int N, int C, int P) {
+// The one argument rule of the four ops and of slak_block_tail_family: C channels, NHWC rows of ldc >= C elements.  ldc == C (the plain entry points):
+// even C; ldc > C (pad columns): ldc % 8 == 0.
+static int tail_args_ok(int N, int C, int P, int ldc) {
     if (N <= 0 || C <= 0 || P <= 0) return SLAK_ERR_INVALID_ARG;
-    if ((C & 1) || C > 1024) return SLAK_ERR_UNSUPPORTED;
-    if ((long long)N * C * P >= (1LL << 31)) return SLAK_ERR_UNSUPPORTED;
-    return SLAK_OK;
-}
-
-// ---- pitched NHWC side: any C <= 1024, rows of ldc >= C elements (ldc % 8 == 0, <= 1024); ldc == C is the plain entry point, bit for bit
-static int tail_args_ok_ld(int N, int C, int P, int ldc) {
-    if (N <= 0 || C <= 0 || P <= 0) return SLAK_ERR_INVALID_ARG;
-    if (C > 1024 || ldc < C || (ldc & 7) || ldc > 1024) return SLAK_ERR_UNSUPPORTED;
+    if (C > 1024 || ldc < C || ldc > 1024 || (ldc == C ? (C & 1) : (ldc & 7))) return SLAK_ERR_UNSUPPORTED;
     if ((long long)N * ldc * P >= (1LL << 31)) return SLAK_ERR_UNSUPPORTED;
     return SLAK_OK;
 }
 
-// The family an entry point runs: the eight of them branch on this function's answer (a family of block_tail_reg.hip: its launcher, which asks
+// The family an entry point runs: the four ops below branch on this function's answer (a family of block_tail_reg.hip: its launcher, which asks
 // the same rt_tail_choice; TILE: the kernels of this file), so the query cannot disagree with the launch.
 int slak_block_tail_family(int op, int shortcut_dtype, int N, int C, int P, int ldc) {
     if (op < SLAK_TAIL_LN_FWD || op > SLAK_TAIL_SR_BWD) return SLAK_TAIL_FAMILY_NONE;
-    if (ldc == C ? tail_args_ok(N, C, P) : tail_args_ok_ld(N, C, P, ldc)) return SLAK_TAIL_FAMILY_NONE;
+    if (tail_args_ok(N, C, P, ldc)) return SLAK_TAIL_FAMILY_NONE;
     if (op == SLAK_TAIL_SR_FWD && shortcut_dtype != SLAK_F32 && shortcut_dtype != SLAK_BF16) return SLAK_TAIL_FAMILY_NONE;
     if (tail_use_reg()) {                               // register-tile and small-plane kernels (block_tail_reg.hip) where an instantiation exists
         const RtChoice ch = rt_tail_choice(op, shortcut_dtype, N, C, ldc, P);
@@ -1286,67 +1280,99 @@ int slak_block_tail_family(int op, int shortcut_dtype, int N, int C, int P, int 
     return SLAK_TAIL_FAMILY_TILE;
 }
 
-int slak_ln_nchw_to_nhwc_forward(const void* x, const float* weight, const float* bias, void* y, float* mean, float* rstd,
-                                 int N, int C, int P, float eps, void* stream) {
+// ---- the four ops, one implementation each.  The LDS-tile kernels come in three sets: ldc == C and C <= 256: one workgroup per 64-pixel tile (_pix);
+// ldc == C and C > 256: persistent workgroups; ldc != C: the persistent kernels with a row pitch (_ld).  Partial rows of the backward ops are [rows][2C]
+// (reduce_partials, which slak_defer_reductions_* can record) except those of a pitched register-family launch: [rows][2 ldc] (reduce_partials_ld).
+static int tail_ln_fwd(const void* x, const float* weight, const float* bias, void* y, float* mean, float* rstd,
+                       int N, int C, int P, float eps, hipStream_t st, int ldc) {
     if (!x || !weight || !bias || !y || !mean || !rstd) return SLAK_ERR_INVALID_ARG;
-    int rc = tail_args_ok(N, C, P); if (rc) return rc;
-    if (slak_block_tail_family(SLAK_TAIL_LN_FWD, 0, N, C, P, C) != SLAK_TAIL_FAMILY_TILE)
-        return launch_ln_nchw_to_nhwc_fwd_reg(x, weight, bias, y, mean, rstd, N, C, P, eps, (hipStream_t)stream);
-    if (C <= 256) {
+    int rc = tail_args_ok(N, C, P, ldc); if (rc) return rc;
+    if (slak_block_tail_family(SLAK_TAIL_LN_FWD, 0, N, C, P, ldc) != SLAK_TAIL_FAMILY_TILE)
+        return launch_ln_nchw_to_nhwc_fwd_reg_ld(x, weight, bias, y, mean, rstd, N, C, ldc, P, eps, st);
+    if (ldc == C && C <= 256) {
         const TailDims d = make_dims_pix(N, C, P);
         const size_t lds = (((size_t)C * (d.TP + 2) * 2 + 15) & ~(size_t)15) + (size_t)(BT_THREADS / d.TP) * d.TP * 4 + 2 * d.TP * 4;
         if (set_lds((const void*)ln_nchw_to_nhwc_fwd_pix_kernel, lds)) return SLAK_ERR_LAUNCH;
-        hipLaunchKernelGGL(ln_nchw_to_nhwc_fwd_pix_kernel, dim3((unsigned)d.ntiles), dim3(BT_THREADS), lds, (hipStream_t)stream,
+        hipLaunchKernelGGL(ln_nchw_to_nhwc_fwd_pix_kernel, dim3((unsigned)d.ntiles), dim3(BT_THREADS), lds, st,
                            (const uint16_t*)x, weight, bias, (uint16_t*)y, mean, rstd, d, eps);
         SLAK_LAUNCH_CHECK();
         return SLAK_OK;
     }
     const TailDims d = make_dims(N, C, P, 2);
     const size_t lds = (size_t)C * (d.TP + 2) * 2 + 16;
-    if (set_lds((const void*)ln_nchw_to_nhwc_fwd_kernel, lds)) return SLAK_ERR_LAUNCH;
-    hipLaunchKernelGGL(ln_nchw_to_nhwc_fwd_kernel, dim3((unsigned)tail_grid(d, lds)), dim3(BT_THREADS), lds, (hipStream_t)stream,
-                       (const uint16_t*)x, weight, bias, (uint16_t*)y, mean, rstd, d, eps);
+    if (ldc == C) {
+        if (set_lds((const void*)ln_nchw_to_nhwc_fwd_kernel, lds)) return SLAK_ERR_LAUNCH;
+        hipLaunchKernelGGL(ln_nchw_to_nhwc_fwd_kernel, dim3((unsigned)tail_grid(d, lds)), dim3(BT_THREADS), lds, st,
+                           (const uint16_t*)x, weight, bias, (uint16_t*)y, mean, rstd, d, eps);
+    } else {
+        if (set_lds((const void*)ln_nchw_to_nhwc_fwd_ld_kernel, lds)) return SLAK_ERR_LAUNCH;
+        hipLaunchKernelGGL(ln_nchw_to_nhwc_fwd_ld_kernel, dim3((unsigned)tail_grid(d, lds)), dim3(BT_THREADS), lds, st,
+                           (const uint16_t*)x, weight, bias, (uint16_t*)y, mean, rstd, d, ldc, eps);
+    }
     SLAK_LAUNCH_CHECK();
     return SLAK_OK;
 }
 
-int slak_ln_nchw_to_nhwc_backward(const void* g, const void* x, const float* weight, const float* mean, const float* rstd,
-                                  void* dx, float* dweight, float* dbias, int N, int C, int P,
-                                  void* workspace, size_t workspace_bytes, void* stream) {
+static int tail_ln_bwd(const void* g, const void* x, const float* weight, const float* mean, const float* rstd,
+                       void* dx, float* dweight, float* dbias, int N, int C, int P,
+                       void* workspace, size_t workspace_bytes, hipStream_t st, int ldc) {
     if (!g || !x || !weight || !mean || !rstd || !dx || !dweight || !dbias) return SLAK_ERR_INVALID_ARG;
-    int rc = tail_args_ok(N, C, P); if (rc) return rc;
-    if (!workspace || workspace_bytes < slak_block_tail_workspace_bytes(N, C, P)) return SLAK_ERR_WORKSPACE;
-    if (slak_block_tail_family(SLAK_TAIL_LN_BWD, 0, N, C, P, C) != SLAK_TAIL_FAMILY_TILE) {
-        int rows = 0; float* part = (float*)workspace;
-        rc = launch_ln_nchw_to_nhwc_bwd_reg(g, x, weight, mean, rstd, dx, part, &rows, N, C, P, (hipStream_t)stream);
-        if (rc == SLAK_OK) return reduce_partials(part, part + (size_t)rows * 2 * C, dweight, dbias, C, rows, 2 * C, (hipStream_t)stream);
-        return rc;
-    }
-    if (C <= 256) {
+    int rc = tail_args_ok(N, C, P, ldc); if (rc) return rc;
+    if (!workspace || workspace_bytes < slak_block_tail_workspace_bytes(N, ldc, P)) return SLAK_ERR_WORKSPACE;
+    float* part = (float*)workspace;
+    int rows = 0;
+    if (slak_block_tail_family(SLAK_TAIL_LN_BWD, 0, N, C, P, ldc) != SLAK_TAIL_FAMILY_TILE) {
+        rc = launch_ln_nchw_to_nhwc_bwd_reg_ld(g, x, weight, mean, rstd, dx, part, &rows, N, C, ldc, P, st);
+        if (rc != SLAK_OK) return rc;
+        if (ldc != C) return reduce_partials_ld(part, dweight, dbias, ldc, C, rows, st);
+    } else if (ldc == C && C <= 256) {
         const TailDims d = make_dims_pix(N, C, P);
         const size_t lds = (((size_t)C * (d.TP + 2) * 2 + 15) & ~(size_t)15) + (((size_t)d.TP * (C + 2) * 2 + 15) & ~(size_t)15) +
                            (size_t)2 * (BT_THREADS / d.TP) * d.TP * 4 + 4 * d.TP * 4;
         if (set_lds((const void*)ln_nchw_to_nhwc_bwd_pix_kernel, lds)) return SLAK_ERR_LAUNCH;
-        float* part = (float*)workspace;
-        hipLaunchKernelGGL(ln_nchw_to_nhwc_bwd_pix_kernel, dim3((unsigned)d.ntiles), dim3(BT_THREADS), lds, (hipStream_t)stream,
+        rows = d.ntiles;
+        hipLaunchKernelGGL(ln_nchw_to_nhwc_bwd_pix_kernel, dim3((unsigned)rows), dim3(BT_THREADS), lds, st,
                            (const uint16_t*)g, (const uint16_t*)x, weight, mean, rstd, (uint16_t*)dx, part, d);
         SLAK_LAUNCH_CHECK();
-        return reduce_partials(part, part + (size_t)d.ntiles * 2 * C, dweight, dbias, C, d.ntiles, 2 * C, (hipStream_t)stream);
+    } else {
+        const TailDims d = make_dims(N, C, P, 2);
+        const size_t lds = (((size_t)C * (d.TP + 2) * 2 + 15) & ~(size_t)15) + (size_t)4 * 2 * C * 4;
+        if (set_lds(ldc == C ? (const void*)ln_nchw_to_nhwc_bwd_kernel : (const void*)ln_nchw_to_nhwc_bwd_ld_kernel, lds)) return SLAK_ERR_LAUNCH;
+        rows = tail_grid(d, lds);
+        if (ldc == C)
+            hipLaunchKernelGGL(ln_nchw_to_nhwc_bwd_kernel, dim3((unsigned)rows), dim3(BT_THREADS), lds, st,
+                               (const uint16_t*)g, (const uint16_t*)x, weight, mean, rstd, (uint16_t*)dx, part, d);
+        else
+            hipLaunchKernelGGL(ln_nchw_to_nhwc_bwd_ld_kernel, dim3((unsigned)rows), dim3(BT_THREADS), lds, st,
+                               (const uint16_t*)g, (const uint16_t*)x, weight, mean, rstd, (uint16_t*)dx, part, d, ldc);
+        SLAK_LAUNCH_CHECK();
     }
-    const TailDims d = make_dims(N, C, P, 2);
-    const size_t lds = (((size_t)C * (d.TP + 2) * 2 + 15) & ~(size_t)15) + (size_t)4 * 2 * C * 4;
-    if (set_lds((const void*)ln_nchw_to_nhwc_bwd_kernel, lds)) return SLAK_ERR_LAUNCH;
-    const int grid = tail_grid(d, lds);
-    float* part = (float*)workspace;
-    hipLaunchKernelGGL(ln_nchw_to_nhwc_bwd_kernel, dim3((unsigned)grid), dim3(BT_THREADS), lds, (hipStream_t)stream,
-                       (const uint16_t*)g, (const uint16_t*)x, weight, mean, rstd, (uint16_t*)dx, part, d);
-    SLAK_LAUNCH_CHECK();
-    return reduce_partials(part, part + (size_t)grid * 2 * C, dweight, dbias, C, grid, 2 * C, (hipStream_t)stream);
+    return reduce_partials(part, part + (size_t)rows * 2 * C, dweight, dbias, C, rows, 2 * C, st);
+}
+
+// the plain entry points: the pitched ones with ldc = C
+int slak_ln_nchw_to_nhwc_forward(const void* x, const float* weight, const float* bias, void* y, float* mean, float* rstd,
+                                 int N, int C, int P, float eps, void* stream) {
+    return tail_ln_fwd(x, weight, bias, y, mean, rstd, N, C, P, eps, (hipStream_t)stream, C);
+}
+int slak_ln_nchw_to_nhwc_forward_ld(const void* x, const float* weight, const float* bias, void* y, float* mean, float* rstd,
+                                    int N, int C, int P, float eps, void* stream, int ldc) {
+    return tail_ln_fwd(x, weight, bias, y, mean, rstd, N, C, P, eps, (hipStream_t)stream, ldc);
+}
+int slak_ln_nchw_to_nhwc_backward(const void* g, const void* x, const float* weight, const float* mean, const float* rstd,
+                                  void* dx, float* dweight, float* dbias, int N, int C, int P,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+    return tail_ln_bwd(g, x, weight, mean, rstd, dx, dweight, dbias, N, C, P, workspace, workspace_bytes, (hipStream_t)stream, C);
+}
+int slak_ln_nchw_to_nhwc_backward_ld(const void* g, const void* x, const float* weight, const float* mean, const float* rstd,
+                                     void* dx, float* dweight, float* dbias, int N, int C, int P,
+                                     void* workspace, size_t workspace_bytes, void* stream, int ldc) {
+    return tail_ln_bwd(g, x, weight, mean, rstd, dx, dweight, dbias, N, C, P, workspace, workspace_bytes, (hipStream_t)stream, ldc);
 }
 
 // LayerNorm(channels_first) of the downsample layers fused with the layout the following Conv2d(k = 2, stride 2) wants as a GEMM operand
 int slak_ln_patch_supported(int N, int C, int H, int W) {
-    if (N <= 0 || H <= 0 || W <= 0 || ((H | W) & 1) || tail_args_ok(N, C, H * W)) return 0;
+    if (N <= 0 || H <= 0 || W <= 0 || ((H | W) & 1) || tail_args_ok(N, C, H * W, C)) return 0;
     return C == 64 || C == 96 || C == 128 || C == 192 || C == 256 || C == 384 || C == 512;
 }
 int slak_ln_patch_forward(const float* x, const float* weight, const float* bias, void* a_bf16, float* mean, float* rstd,
@@ -1456,175 +1482,101 @@ int slak_channel_sums_bf16(const void* x_bf16, float* out, int N, int C, int P, 
     return reduce_partials((const float*)workspace, nullptr, out, out, C, S, C, (hipStream_t)stream);
 }
 
-int slak_scale_residual_forward(const void* shortcut, int shortcut_dtype, const void* z, const float* gamma, const float* sample_scale,
-                                float* out, void* out_bf16, int N, int C, int P, void* stream) {
+static int tail_sr_fwd(const void* shortcut, int shortcut_dtype, const void* z, const float* gamma, const float* sample_scale,
+                       float* out, void* out_bf16, int N, int C, int P, hipStream_t st, int ldc) {
     if (!shortcut || !z || !gamma || !out) return SLAK_ERR_INVALID_ARG;
-    int rc = tail_args_ok(N, C, P); if (rc) return rc;
-    {
-        const int fam = slak_block_tail_family(SLAK_TAIL_SR_FWD, shortcut_dtype, N, C, P, C);
-        if (fam == SLAK_TAIL_FAMILY_NONE) return SLAK_ERR_UNSUPPORTED;             // (the shortcut's dtype)
-        if (fam != SLAK_TAIL_FAMILY_TILE)
-            return launch_scale_residual_fwd_reg(shortcut, shortcut_dtype, z, gamma, sample_scale, out, out_bf16, N, C, P, (hipStream_t)stream);
-    }
-    if (C <= 256) {
+    int rc = tail_args_ok(N, C, P, ldc); if (rc) return rc;
+    const int fam = slak_block_tail_family(SLAK_TAIL_SR_FWD, shortcut_dtype, N, C, P, ldc);
+    if (fam == SLAK_TAIL_FAMILY_NONE) return SLAK_ERR_UNSUPPORTED;                 // (the shortcut's dtype)
+    if (fam != SLAK_TAIL_FAMILY_TILE)
+        return launch_scale_residual_fwd_reg_ld(shortcut, shortcut_dtype, z, gamma, sample_scale, out, out_bf16, N, C, ldc, P, st);
+    // KERNEL<the shortcut's type> on GRID workgroups; the variadic part: what the kernel takes behind out_bf16
+#define SLAK_SR_FWD_TILE(KERNEL, TSC, GRID, ...)                                                                                       \
+    do {                                                                                                                               \
+        if (set_lds((const void*)KERNEL<TSC>, lds)) return SLAK_ERR_LAUNCH;                                                            \
+        hipLaunchKernelGGL(KERNEL<TSC>, GRID, dim3(BT_THREADS), lds, st, (const TSC*)shortcut, (const uint16_t*)z, gamma, sample_scale, \
+                           out, (uint16_t*)out_bf16, __VA_ARGS__);                                                                     \
+    } while (0)
+    if (ldc == C && C <= 256) {
         const TailDims d = make_dims_pix(N, C, P);
         const size_t lds = (size_t)d.TP * (C + 2) * 2 + 16;
         const dim3 grid((unsigned)d.ntiles);
-        if (shortcut_dtype == SLAK_F32) {
-            if (set_lds((const void*)scale_residual_fwd_pix_kernel<float>, lds)) return SLAK_ERR_LAUNCH;
-            hipLaunchKernelGGL(scale_residual_fwd_pix_kernel<float>, grid, dim3(BT_THREADS), lds, (hipStream_t)stream,
-                               (const float*)shortcut, (const uint16_t*)z, gamma, sample_scale, out, (uint16_t*)out_bf16, d);
-        } else if (shortcut_dtype == SLAK_BF16) {
-            if (set_lds((const void*)scale_residual_fwd_pix_kernel<bf16_t>, lds)) return SLAK_ERR_LAUNCH;
-            hipLaunchKernelGGL(scale_residual_fwd_pix_kernel<bf16_t>, grid, dim3(BT_THREADS), lds, (hipStream_t)stream,
-                               (const bf16_t*)shortcut, (const uint16_t*)z, gamma, sample_scale, out, (uint16_t*)out_bf16, d);
-        } else return SLAK_ERR_UNSUPPORTED;
-        SLAK_LAUNCH_CHECK();
-        return SLAK_OK;
+        if (shortcut_dtype == SLAK_F32) SLAK_SR_FWD_TILE(scale_residual_fwd_pix_kernel, float, grid, d);
+        else SLAK_SR_FWD_TILE(scale_residual_fwd_pix_kernel, bf16_t, grid, d);
+    } else {
+        const int zp = 2 * ((C + 1) / 2) + 2;                       // the NHWC tile is [TP][zp] (C + 2 for the even C of a plain call): same byte count as [C][TP+2] up to the padding
+        TailDims d = make_dims(N, C, P, 2);
+        while (d.TP > 16 && (size_t)d.TP * zp * 2 > 50 * 1024) { d.TP /= 2; d.tiles_per_image = (P + d.TP - 1) / d.TP; d.ntiles = N * d.tiles_per_image; }
+        const size_t lds = (size_t)d.TP * zp * 2 + 16;
+        const dim3 grid((unsigned)tail_grid(d, lds));
+        if (ldc == C) {
+            if (shortcut_dtype == SLAK_F32) SLAK_SR_FWD_TILE(scale_residual_fwd_kernel, float, grid, d);
+            else SLAK_SR_FWD_TILE(scale_residual_fwd_kernel, bf16_t, grid, d);
+        } else {
+            if (shortcut_dtype == SLAK_F32) SLAK_SR_FWD_TILE(scale_residual_fwd_ld_kernel, float, grid, d, ldc);
+            else SLAK_SR_FWD_TILE(scale_residual_fwd_ld_kernel, bf16_t, grid, d, ldc);
+        }
     }
-    TailDims d = make_dims(N, C, P, 2);
-    // the NHWC tile is [TP][C+2]: same byte count as [C][TP+2] up to the padding
-    while (d.TP > 16 && (size_t)d.TP * (C + 2) * 2 > 50 * 1024) { d.TP /= 2; d.tiles_per_image = (P + d.TP - 1) / d.TP; d.ntiles = N * d.tiles_per_image; }
-    const size_t lds = (size_t)d.TP * (C + 2) * 2 + 16;
-    const dim3 grid((unsigned)tail_grid(d, lds));
-    if (shortcut_dtype == SLAK_F32) {
-        if (set_lds((const void*)scale_residual_fwd_kernel<float>, lds)) return SLAK_ERR_LAUNCH;
-        hipLaunchKernelGGL(scale_residual_fwd_kernel<float>, grid, dim3(BT_THREADS), lds, (hipStream_t)stream,
-                           (const float*)shortcut, (const uint16_t*)z, gamma, sample_scale, out, (uint16_t*)out_bf16, d);
-    } else if (shortcut_dtype == SLAK_BF16) {
-        if (set_lds((const void*)scale_residual_fwd_kernel<bf16_t>, lds)) return SLAK_ERR_LAUNCH;
-        hipLaunchKernelGGL(scale_residual_fwd_kernel<bf16_t>, grid, dim3(BT_THREADS), lds, (hipStream_t)stream,
-                           (const bf16_t*)shortcut, (const uint16_t*)z, gamma, sample_scale, out, (uint16_t*)out_bf16, d);
-    } else return SLAK_ERR_UNSUPPORTED;
+#undef SLAK_SR_FWD_TILE
     SLAK_LAUNCH_CHECK();
     return SLAK_OK;
 }
 
-int slak_scale_residual_backward(const float* dout, const void* dout_bf16, float* dout_sum, const void* z, const float* gamma,
-                                 const float* sample_scale, void* dz, float* dgamma, float* dz_colsum, int N, int C, int P,
-                                 void* workspace, size_t workspace_bytes, void* stream) {
+static int tail_sr_bwd(const float* dout, const void* dout_bf16, float* dout_sum, const void* z, const float* gamma,
+                       const float* sample_scale, void* dz, float* dgamma, float* dz_colsum, int N, int C, int P,
+                       void* workspace, size_t workspace_bytes, hipStream_t st, int ldc) {
     if (!dout || !z || !gamma || !dz || !dgamma || !dz_colsum || (dout_bf16 && !dout_sum)) return SLAK_ERR_INVALID_ARG;
-    int rc = tail_args_ok(N, C, P); if (rc) return rc;
-    if (!workspace || workspace_bytes < slak_block_tail_workspace_bytes(N, C, P)) return SLAK_ERR_WORKSPACE;
-    if (slak_block_tail_family(SLAK_TAIL_SR_BWD, 0, N, C, P, C) != SLAK_TAIL_FAMILY_TILE) {
-        int rows = 0; float* part = (float*)workspace;
-        rc = launch_scale_residual_bwd_reg(dout, dout_bf16, dout_sum, z, gamma, sample_scale, dz, part, &rows, N, C, P, (hipStream_t)stream);
-        if (rc == SLAK_OK) return reduce_partials(part, part + (size_t)rows * 2 * C, dgamma, dz_colsum, C, rows, 2 * C, (hipStream_t)stream);
-        return rc;
-    }
-    if (C <= 256) {
+    int rc = tail_args_ok(N, C, P, ldc); if (rc) return rc;
+    if (!workspace || workspace_bytes < slak_block_tail_workspace_bytes(N, ldc, P)) return SLAK_ERR_WORKSPACE;
+    float* part = (float*)workspace;
+    int rows = 0;
+    if (slak_block_tail_family(SLAK_TAIL_SR_BWD, 0, N, C, P, ldc) != SLAK_TAIL_FAMILY_TILE) {
+        rc = launch_scale_residual_bwd_reg_ld(dout, dout_bf16, dout_sum, z, gamma, sample_scale, dz, part, &rows, N, C, ldc, P, st);
+        if (rc != SLAK_OK) return rc;
+        if (ldc != C) return reduce_partials_ld(part, dgamma, dz_colsum, ldc, C, rows, st);
+    } else if (ldc == C && C <= 256) {
         const TailDims d = make_dims_pix(N, C, P);
         const size_t lds = (size_t)C * (d.TP + 1) * 4 + (size_t)d.TP * (C + 2) * 2 + 16;
         if (set_lds((const void*)scale_residual_bwd_pix_kernel, lds)) return SLAK_ERR_LAUNCH;
-        float* part = (float*)workspace;
-        hipLaunchKernelGGL(scale_residual_bwd_pix_kernel, dim3((unsigned)d.ntiles), dim3(BT_THREADS), lds, (hipStream_t)stream,
+        rows = d.ntiles;
+        hipLaunchKernelGGL(scale_residual_bwd_pix_kernel, dim3((unsigned)rows), dim3(BT_THREADS), lds, st,
                            dout, (const uint16_t*)dout_bf16, dout_sum, (const uint16_t*)z, gamma, sample_scale, (uint16_t*)dz, part, d);
         SLAK_LAUNCH_CHECK();
-        return reduce_partials(part, part + (size_t)d.ntiles * 2 * C, dgamma, dz_colsum, C, d.ntiles, 2 * C, (hipStream_t)stream);
+    } else {
+        const TailDims d = make_dims(N, C, P, 4);
+        const size_t red = (size_t)(ldc == C ? 4 : 8) * C * 4 + 16;     // the per-wave partial sums reuse the tile: [4][C], the _ld kernel 2 x [4][C]
+        size_t lds = (size_t)C * (d.TP + 1) * 4 + 16;
+        if (lds < red) lds = red;
+        if (set_lds(ldc == C ? (const void*)scale_residual_bwd_kernel : (const void*)scale_residual_bwd_ld_kernel, lds)) return SLAK_ERR_LAUNCH;
+        rows = tail_grid(d, lds);
+        if (ldc == C)
+            hipLaunchKernelGGL(scale_residual_bwd_kernel, dim3((unsigned)rows), dim3(BT_THREADS), lds, st,
+                               dout, (const uint16_t*)dout_bf16, dout_sum, (const uint16_t*)z, gamma, sample_scale, (uint16_t*)dz, part, d);
+        else
+            hipLaunchKernelGGL(scale_residual_bwd_ld_kernel, dim3((unsigned)rows), dim3(BT_THREADS), lds, st,
+                               dout, (const uint16_t*)dout_bf16, dout_sum, (const uint16_t*)z, gamma, sample_scale, (uint16_t*)dz, part, d, ldc);
+        SLAK_LAUNCH_CHECK();
     }
-    const TailDims d = make_dims(N, C, P, 4);
-    size_t lds = (size_t)C * (d.TP + 1) * 4 + 16;
-    if (lds < (size_t)4 * C * 4 + 16) lds = (size_t)4 * C * 4 + 16;
-    if (set_lds((const void*)scale_residual_bwd_kernel, lds)) return SLAK_ERR_LAUNCH;
-    const int grid = tail_grid(d, lds);
-    float* part = (float*)workspace;
-    hipLaunchKernelGGL(scale_residual_bwd_kernel, dim3((unsigned)grid), dim3(BT_THREADS), lds, (hipStream_t)stream,
-                       dout, (const uint16_t*)dout_bf16, dout_sum, (const uint16_t*)z, gamma, sample_scale, (uint16_t*)dz, part, d);
-    SLAK_LAUNCH_CHECK();
-    return reduce_partials(part, part + (size_t)grid * 2 * C, dgamma, dz_colsum, C, grid, 2 * C, (hipStream_t)stream);
+    return reduce_partials(part, part + (size_t)rows * 2 * C, dgamma, dz_colsum, C, rows, 2 * C, st);
 }
 
-// ---- the pitched entry points (tail_args_ok_ld above)
-int slak_ln_nchw_to_nhwc_forward_ld(const void* x, const float* weight, const float* bias, void* y, float* mean, float* rstd,
-                                    int N, int C, int P, float eps, void* stream, int ldc) {
-    if (!x || !weight || !bias || !y || !mean || !rstd) return SLAK_ERR_INVALID_ARG;
-    int rc = tail_args_ok_ld(N, C, P, ldc); if (rc) return rc;
-    if (ldc == C) return slak_ln_nchw_to_nhwc_forward(x, weight, bias, y, mean, rstd, N, C, P, eps, stream);
-    if (slak_block_tail_family(SLAK_TAIL_LN_FWD, 0, N, C, P, ldc) != SLAK_TAIL_FAMILY_TILE)       // small-plane family, or the register-tile kernel whose channel count is the pitch
-        return launch_ln_nchw_to_nhwc_fwd_reg_ld(x, weight, bias, y, mean, rstd, N, C, ldc, P, eps, (hipStream_t)stream);
-    const TailDims d = make_dims(N, C, P, 2);
-    const size_t lds = (size_t)C * (d.TP + 2) * 2 + 16;
-    if (set_lds((const void*)ln_nchw_to_nhwc_fwd_ld_kernel, lds)) return SLAK_ERR_LAUNCH;
-    hipLaunchKernelGGL(ln_nchw_to_nhwc_fwd_ld_kernel, dim3((unsigned)tail_grid(d, lds)), dim3(BT_THREADS), lds, (hipStream_t)stream,
-                       (const uint16_t*)x, weight, bias, (uint16_t*)y, mean, rstd, d, ldc, eps);
-    SLAK_LAUNCH_CHECK();
-    return SLAK_OK;
+int slak_scale_residual_forward(const void* shortcut, int shortcut_dtype, const void* z, const float* gamma, const float* sample_scale,
+                                float* out, void* out_bf16, int N, int C, int P, void* stream) {
+    return tail_sr_fwd(shortcut, shortcut_dtype, z, gamma, sample_scale, out, out_bf16, N, C, P, (hipStream_t)stream, C);
 }
-
-int slak_ln_nchw_to_nhwc_backward_ld(const void* g, const void* x, const float* weight, const float* mean, const float* rstd,
-                                     void* dx, float* dweight, float* dbias, int N, int C, int P,
-                                     void* workspace, size_t workspace_bytes, void* stream, int ldc) {
-    if (!g || !x || !weight || !mean || !rstd || !dx || !dweight || !dbias) return SLAK_ERR_INVALID_ARG;
-    int rc = tail_args_ok_ld(N, C, P, ldc); if (rc) return rc;
-    if (ldc == C) return slak_ln_nchw_to_nhwc_backward(g, x, weight, mean, rstd, dx, dweight, dbias, N, C, P, workspace, workspace_bytes, stream);
-    if (!workspace || workspace_bytes < slak_block_tail_workspace_bytes(N, ldc, P)) return SLAK_ERR_WORKSPACE;
-    if (slak_block_tail_family(SLAK_TAIL_LN_BWD, 0, N, C, P, ldc) != SLAK_TAIL_FAMILY_TILE) {
-        int rows = 0;
-        rc = launch_ln_nchw_to_nhwc_bwd_reg_ld(g, x, weight, mean, rstd, dx, (float*)workspace, &rows, N, C, ldc, P, (hipStream_t)stream);
-        if (rc == SLAK_OK) return reduce_partials_ld((const float*)workspace, dweight, dbias, ldc, C, rows, (hipStream_t)stream);
-        return rc;
-    }
-    const TailDims d = make_dims(N, C, P, 2);
-    const size_t lds = (((size_t)C * (d.TP + 2) * 2 + 15) & ~(size_t)15) + (size_t)4 * 2 * C * 4;
-    if (set_lds((const void*)ln_nchw_to_nhwc_bwd_ld_kernel, lds)) return SLAK_ERR_LAUNCH;
-    const int grid = tail_grid(d, lds);
-    float* part = (float*)workspace;
-    hipLaunchKernelGGL(ln_nchw_to_nhwc_bwd_ld_kernel, dim3((unsigned)grid), dim3(BT_THREADS), lds, (hipStream_t)stream,
-                       (const uint16_t*)g, (const uint16_t*)x, weight, mean, rstd, (uint16_t*)dx, part, d, ldc);
-    SLAK_LAUNCH_CHECK();
-    return reduce_partials(part, part + (size_t)grid * 2 * C, dweight, dbias, C, grid, 2 * C, (hipStream_t)stream);
-}
-
 int slak_scale_residual_forward_ld(const void* shortcut, int shortcut_dtype, const void* z, const float* gamma, const float* sample_scale,
                                    float* out, void* out_bf16, int N, int C, int P, void* stream, int ldc) {
-    if (!shortcut || !z || !gamma || !out) return SLAK_ERR_INVALID_ARG;
-    int rc = tail_args_ok_ld(N, C, P, ldc); if (rc) return rc;
-    if (ldc == C) return slak_scale_residual_forward(shortcut, shortcut_dtype, z, gamma, sample_scale, out, out_bf16, N, C, P, stream);
-    if (shortcut_dtype != SLAK_F32 && shortcut_dtype != SLAK_BF16) return SLAK_ERR_UNSUPPORTED;
-    if (slak_block_tail_family(SLAK_TAIL_SR_FWD, shortcut_dtype, N, C, P, ldc) != SLAK_TAIL_FAMILY_TILE)
-        return launch_scale_residual_fwd_reg_ld(shortcut, shortcut_dtype, z, gamma, sample_scale, out, out_bf16, N, C, ldc, P, (hipStream_t)stream);
-    const int zp = 2 * ((C + 1) / 2) + 2;                           // the NHWC tile is [TP][zp]: same byte count as [C][TP+2] up to the padding
-    TailDims d = make_dims(N, C, P, 2);
-    while (d.TP > 16 && (size_t)d.TP * zp * 2 > 50 * 1024) { d.TP /= 2; d.tiles_per_image = (P + d.TP - 1) / d.TP; d.ntiles = N * d.tiles_per_image; }
-    const size_t lds = (size_t)d.TP * zp * 2 + 16;
-    const dim3 grid((unsigned)tail_grid(d, lds));
-    if (shortcut_dtype == SLAK_F32) {
-        if (set_lds((const void*)scale_residual_fwd_ld_kernel<float>, lds)) return SLAK_ERR_LAUNCH;
-        hipLaunchKernelGGL(scale_residual_fwd_ld_kernel<float>, grid, dim3(BT_THREADS), lds, (hipStream_t)stream,
-                           (const float*)shortcut, (const uint16_t*)z, gamma, sample_scale, out, (uint16_t*)out_bf16, d, ldc);
-    } else {
-        if (set_lds((const void*)scale_residual_fwd_ld_kernel<bf16_t>, lds)) return SLAK_ERR_LAUNCH;
-        hipLaunchKernelGGL(scale_residual_fwd_ld_kernel<bf16_t>, grid, dim3(BT_THREADS), lds, (hipStream_t)stream,
-                           (const bf16_t*)shortcut, (const uint16_t*)z, gamma, sample_scale, out, (uint16_t*)out_bf16, d, ldc);
-    }
-    SLAK_LAUNCH_CHECK();
-    return SLAK_OK;
+    return tail_sr_fwd(shortcut, shortcut_dtype, z, gamma, sample_scale, out, out_bf16, N, C, P, (hipStream_t)stream, ldc);
 }
-
+int slak_scale_residual_backward(const float* dout, const void* dout_bf16, float* dout_sum, const void* z, const float* gamma,
+                                 const float* sample_scale, void* dz, float* dgamma, float* dz_colsum, int N, int C, int P,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+    return tail_sr_bwd(dout, dout_bf16, dout_sum, z, gamma, sample_scale, dz, dgamma, dz_colsum, N, C, P, workspace, workspace_bytes, (hipStream_t)stream, C);
+}
 int slak_scale_residual_backward_ld(const float* dout, const void* dout_bf16, float* dout_sum, const void* z, const float* gamma,
                                     const float* sample_scale, void* dz, float* dgamma, float* dz_colsum, int N, int C, int P,
                                     void* workspace, size_t workspace_bytes, void* stream, int ldc) {
-    if (!dout || !z || !gamma || !dz || !dgamma || !dz_colsum || (dout_bf16 && !dout_sum)) return SLAK_ERR_INVALID_ARG;
-    int rc = tail_args_ok_ld(N, C, P, ldc); if (rc) return rc;
-    if (ldc == C) return slak_scale_residual_backward(dout, dout_bf16, dout_sum, z, gamma, sample_scale, dz, dgamma, dz_colsum, N, C, P,
-                                                      workspace, workspace_bytes, stream);
-    if (!workspace || workspace_bytes < slak_block_tail_workspace_bytes(N, ldc, P)) return SLAK_ERR_WORKSPACE;
-    if (slak_block_tail_family(SLAK_TAIL_SR_BWD, 0, N, C, P, ldc) != SLAK_TAIL_FAMILY_TILE) {
-        int rows = 0;
-        rc = launch_scale_residual_bwd_reg_ld(dout, dout_bf16, dout_sum, z, gamma, sample_scale, dz, (float*)workspace, &rows, N, C, ldc, P, (hipStream_t)stream);
-        if (rc == SLAK_OK) return reduce_partials_ld((const float*)workspace, dgamma, dz_colsum, ldc, C, rows, (hipStream_t)stream);
-        return rc;
-    }
-    const TailDims d = make_dims(N, C, P, 4);
-    size_t lds = (size_t)C * (d.TP + 1) * 4 + 16;
-    if (lds < (size_t)8 * C * 4 + 16) lds = (size_t)8 * C * 4 + 16;               // the per-wave partial sums reuse the tile: 2 x [4][C]
-    if (set_lds((const void*)scale_residual_bwd_ld_kernel, lds)) return SLAK_ERR_LAUNCH;
-    const int grid = tail_grid(d, lds);
-    float* part = (float*)workspace;
-    hipLaunchKernelGGL(scale_residual_bwd_ld_kernel, dim3((unsigned)grid), dim3(BT_THREADS), lds, (hipStream_t)stream,
-                       dout, (const uint16_t*)dout_bf16, dout_sum, (const uint16_t*)z, gamma, sample_scale, (uint16_t*)dz, part, d, ldc);
-    SLAK_LAUNCH_CHECK();
-    return reduce_partials(part, part + (size_t)grid * 2 * C, dgamma, dz_colsum, C, grid, 2 * C, (hipStream_t)stream);
+    return tail_sr_bwd(dout, dout_bf16, dout_sum, z, gamma, sample_scale, dz, dgamma, dz_colsum, N, C, P, workspace, workspace_bytes, (hipStream_t)stream, ldc);
 }
 
 static int cf_block(int N, int P) { return (long long)N * ((P + BT_THREADS - 1) / BT_THREADS) >= 1024 ? BT_THREADS : 64; }

@@ -1168,7 +1168,7 @@ static bool rt_reg_has(int C, int P) { return !(P & 1) && (C == 64 || C == 96 ||
     }
 static bool rt_reg_ld_has(int Cl, int ldc, int P) { return !(P & 1) && Cl <= ldc && ldc - Cl <= RT_LD_PAD && (ldc == 128 || ldc == 256 || ldc == 512); }
 
-// WHICH family runs op (SLAK_TAIL_*) on (N, Cl, ldc, P), and with how many channels per wave: the one decision that the eight launchers below and
+// WHICH family runs op (SLAK_TAIL_*) on (N, Cl, ldc, P), and with how many channels per wave: the one decision that the four launchers below and
 // slak_block_tail_family share.  Host code only, no device call.  Cl == ldc is a plain call.  A pitched call takes the small-plane families exactly
 // where the plain call on C = ldc takes them (the predicates see the pitch: the groups tile it), ahead of the pixel-pair kernels; one rung is the
 // pitched calls' own: the LayerNorm kernels on odd planes with 64 channels per wave where 48 / 32 would need more than 16 waves (ldc = 1024: C = 998).
@@ -1222,9 +1222,6 @@ int launch_ln_nchw_to_nhwc_fwd_reg_ld(const void* x, const float* w, const float
     SLAK_RT_DISPATCH(ldc, CALL)
 #undef CALL
 }
-int launch_ln_nchw_to_nhwc_fwd_reg(const void* x, const float* w, const float* b, void* y, float* mean, float* rstd, int N, int C, int P, float eps, hipStream_t st) {
-    return launch_ln_nchw_to_nhwc_fwd_reg_ld(x, w, b, y, mean, rstd, N, C, C, P, eps, st);
-}
 int launch_ln_nchw_to_nhwc_bwd_reg_ld(const void* g, const void* x, const float* w, const float* mean, const float* rstd, void* dx, float* part, int* rows,
                                       int N, int Cl, int ldc, int P, hipStream_t st) {
     const RtChoice ch = rt_tail_choice(SLAK_TAIL_LN_BWD, 0, N, Cl, ldc, P);
@@ -1247,10 +1244,6 @@ int launch_ln_nchw_to_nhwc_bwd_reg_ld(const void* g, const void* x, const float*
 #define CALL(CL, G) return launch_ln_bwd_reg<CL, G>((const uint16_t*)g, (const uint16_t*)x, w, mean, rstd, (uint16_t*)dx, part, rows, N, P, st)
     SLAK_RT_DISPATCH(ldc, CALL)
 #undef CALL
-}
-int launch_ln_nchw_to_nhwc_bwd_reg(const void* g, const void* x, const float* w, const float* mean, const float* rstd, void* dx, float* part, int* rows,
-                                   int N, int C, int P, hipStream_t st) {
-    return launch_ln_nchw_to_nhwc_bwd_reg_ld(g, x, w, mean, rstd, dx, part, rows, N, C, C, P, st);
 }
 // LayerNorm(channels_first) of an fp32 NCHW tensor written as the bf16 patch matrix of a 2x2 / stride-2 convolution, and its backward
 int launch_ln_patch_fwd_reg(const float* x, const float* w, const float* b, void* a, float* mean, float* rstd, int N, int C, int H, int W, float eps, hipStream_t st) {
@@ -1305,10 +1298,6 @@ int launch_scale_residual_fwd_reg_ld(const void* sc, int sc_dtype, const void* z
     }
     return SLAK_ERR_UNSUPPORTED;
 }
-int launch_scale_residual_fwd_reg(const void* sc, int sc_dtype, const void* z, const float* gamma, const float* scale, float* out, void* out16,
-                                  int N, int C, int P, hipStream_t st) {
-    return launch_scale_residual_fwd_reg_ld(sc, sc_dtype, z, gamma, scale, out, out16, N, C, C, P, st);
-}
 int launch_scale_residual_bwd_reg_ld(const float* dout, const void* dout16, float* dsum, const void* z, const float* gamma, const float* scale, void* dz,
                                      float* part, int* rows, int N, int Cl, int ldc, int P, hipStream_t st) {
     const RtChoice ch = rt_tail_choice(SLAK_TAIL_SR_BWD, 0, N, Cl, ldc, P);
@@ -1330,10 +1319,6 @@ int launch_scale_residual_bwd_reg_ld(const float* dout, const void* dout16, floa
 #define CALL(CL, G) return launch_sr_bwd_reg<CL, G>(dout, (const uint16_t*)dout16, dsum, (const uint16_t*)z, gamma, scale, (uint16_t*)dz, part, rows, N, P, st)
     SLAK_RT_DISPATCH(ldc, CALL)
 #undef CALL
-}
-int launch_scale_residual_bwd_reg(const float* dout, const void* dout16, float* dsum, const void* z, const float* gamma, const float* scale, void* dz,
-                                  float* part, int* rows, int N, int C, int P, hipStream_t st) {
-    return launch_scale_residual_bwd_reg_ld(dout, dout16, dsum, z, gamma, scale, dz, part, rows, N, C, C, P, st);
 }
 
 }  // namespace slak

@@ -260,22 +260,15 @@ __device__ __forceinline__ void wgrad_finish(const float* partial, float* dw, un
 #endif
 
 // block_tail_reg.hip: register-tile block-tail kernels (C <= 256 classes); SLAK_ERR_UNSUPPORTED = no instantiation for C
-int launch_ln_nchw_to_nhwc_fwd_reg(const void* x, const float* w, const float* b, void* y, float* mean, float* rstd, int N, int C, int P, float eps, hipStream_t st);
-int launch_ln_nchw_to_nhwc_bwd_reg(const void* g, const void* x, const float* w, const float* mean, const float* rstd, void* dx, float* part, int* rows,
-                                   int N, int C, int P, hipStream_t st);       // *rows = partial rows written ([rows][2C]); the caller reduces them
 int launch_ln_patch_fwd_reg(const float* x, const float* w, const float* b, void* a, float* mean, float* rstd, int N, int C, int H, int W, float eps, hipStream_t st);
 int launch_ln_patch_bwd_reg(const void* g, const float* x, const float* w, const float* mean, const float* rstd, float* dx, float* part, int* rows,
-                            int N, int C, int H, int W, hipStream_t st);
-int launch_scale_residual_fwd_reg(const void* sc, int sc_dtype, const void* z, const float* gamma, const float* scale, float* out, void* out16,
-                                  int N, int C, int P, hipStream_t st);
-int launch_scale_residual_bwd_reg(const float* dout, const void* dout16, float* dsum, const void* z, const float* gamma, const float* scale, void* dz,
-                                  float* part, int* rows, int N, int C, int P, hipStream_t st);
+                            int N, int C, int H, int W, hipStream_t st);       // *rows = partial rows written ([rows][2C]); the caller reduces them
 // which family of that file runs op (SLAK_TAIL_*) and on how many channels per wave; Cl == ldc: a plain call.  Host code, no device call.  The launchers
-// above and below ask it themselves (SLAK_TAIL_FAMILY_NONE <-> SLAK_ERR_UNSUPPORTED), slak_block_tail_family reports it.
+// below ask it themselves (SLAK_TAIL_FAMILY_NONE <-> SLAK_ERR_UNSUPPORTED), slak_block_tail_family reports it.
 struct RtChoice { int family, cw; };
 RtChoice rt_tail_choice(int op, int sc_dtype, int N, int Cl, int ldc, int P);
-// ... and the same kernels for the pitched entry points: Cl channel rows on the NCHW side, rows of ldc on the NHWC side (the small-plane families: any ldc their
-// channel groups tile; the pixel-pair kernels: 128 / 256 / 512); partial rows [rows][2 ldc]
+// the four block-tail ops: Cl channel rows on the NCHW side, rows of ldc on the NHWC side (Cl == ldc: every instantiation; pitched: the small-plane families on any
+// ldc their channel groups tile, the pixel-pair kernels on 128 / 256 / 512); partial rows [rows][2 ldc], the caller reduces them
 int launch_ln_nchw_to_nhwc_fwd_reg_ld(const void* x, const float* w, const float* b, void* y, float* mean, float* rstd, int N, int Cl, int ldc, int P, float eps, hipStream_t st);
 int launch_ln_nchw_to_nhwc_bwd_reg_ld(const void* g, const void* x, const float* w, const float* mean, const float* rstd, void* dx, float* part, int* rows,
                                       int N, int Cl, int ldc, int P, hipStream_t st);

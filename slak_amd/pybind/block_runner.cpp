@@ -232,15 +232,11 @@ std::vector<Tensor> block_forward(const Tensor& x, const c10::optional<Tensor>& 
                                         gam, bet, rm, rv, (float)bn_eps, (float)bn_momentum, 1, update_running ? 1 : 0, fpm(coef), fpm(bnstats), sum.data_ptr(),
                                         s.N, s.C, s.P, st), "slak_bn3_forward_apply");
     }
-    // permute + LayerNorm
-    const bool pitched = s.Cp != s.C;
+    // permute + LayerNorm (rows of Cp; Cp == C: the plain block)
     Tensor t = at::empty({s.N, s.H, s.W, s.Cp}, x16.options());
     Tensor mean = at::empty({s.N, s.P}, stats.options()), rstd = at::empty({s.N, s.P}, stats.options());
-    if (pitched) check_rc(slak_ln_nchw_to_nhwc_forward_ld(sum.data_ptr(), fp(lnw), fp(lnb), t.data_ptr(), fpm(mean), fpm(rstd), s.N, s.C, s.P, (float)ln_eps, st, s.Cp),
-                          "slak_ln_nchw_to_nhwc_forward_ld");
-    else
-    check_rc(slak_ln_nchw_to_nhwc_forward(sum.data_ptr(), fp(lnw), fp(lnb), t.data_ptr(), fpm(mean), fpm(rstd), s.N, s.C, s.P, (float)ln_eps, st),
-             "slak_ln_nchw_to_nhwc_forward");
+    check_rc(slak_ln_nchw_to_nhwc_forward_ld(sum.data_ptr(), fp(lnw), fp(lnb), t.data_ptr(), fpm(mean), fpm(rstd), s.N, s.C, s.P, (float)ln_eps, st, s.Cp),
+             "slak_ln_nchw_to_nhwc_forward_ld");
     // pwconv1 -> GELU -> pwconv2
     Tensor y1m, a, z;
     if (pl.mlp1) {                                                 // stage 1: pwconv1, GELU and pwconv2 in one pass
@@ -272,13 +268,9 @@ std::vector<Tensor> block_forward(const Tensor& x, const c10::optional<Tensor>& 
     Tensor out = at::empty({s.N, s.C, s.H, s.W}, stats.options());
     Tensor out16 = emit_lowp ? at::empty({s.N, s.C, s.H, s.W}, x16.options()) : Tensor();
     const bool has_scale = sample_scale.has_value() && sample_scale->defined();
-    if (pitched) check_rc(slak_scale_residual_forward_ld(x.data_ptr(), x.scalar_type() == at::kFloat ? SLAK_F32 : SLAK_BF16, z.data_ptr(), fp(gamma),
-                                                         has_scale ? fp(*sample_scale) : nullptr, fpm(out), emit_lowp ? out16.data_ptr() : nullptr, s.N, s.C, s.P, st, s.Cp),
-                          "slak_scale_residual_forward_ld");
-    else
-    check_rc(slak_scale_residual_forward(x.data_ptr(), x.scalar_type() == at::kFloat ? SLAK_F32 : SLAK_BF16, z.data_ptr(), fp(gamma),
-                                         has_scale ? fp(*sample_scale) : nullptr, fpm(out), emit_lowp ? out16.data_ptr() : nullptr, s.N, s.C, s.P, st),
-             "slak_scale_residual_forward");
+    check_rc(slak_scale_residual_forward_ld(x.data_ptr(), x.scalar_type() == at::kFloat ? SLAK_F32 : SLAK_BF16, z.data_ptr(), fp(gamma),
+                                            has_scale ? fp(*sample_scale) : nullptr, fpm(out), emit_lowp ? out16.data_ptr() : nullptr, s.N, s.C, s.P, st, s.Cp),
+             "slak_scale_residual_forward_ld");
     return {out, out16, x16, yv, yh, ys, bnstats, sum, t, mean, rstd, y1m, a, z, count_dev};
 }
 
@@ -364,14 +356,10 @@ std::vector<Tensor> block_backward(const Tensor& x16, const Tensor& wv, const Te
     Tensor dsum = dout16.defined() ? at::empty_like(dout) : Tensor();
     Tensor dz = at::empty_like(z), dgamma = gd.take(G_GAMMA, {s.C}, f32), dzc = gd.take(G_BB2, {s.C}, f32);
     const bool has_scale = sample_scale.has_value() && sample_scale->defined();
-    if (pitched)                                                   // (a final reduction the library cannot defer runs at once: the same sums)
+    // (a pitched block's final reduction that the library cannot defer runs at once: the same sums)
     check_rc(slak_scale_residual_backward_ld(fp(dout), dout16.defined() ? dout16.data_ptr() : nullptr, dsum.defined() ? fpm(dsum) : nullptr, z.data_ptr(),
                                              fp(gamma), has_scale ? fp(*sample_scale) : nullptr, dz.data_ptr(), fpm(dgamma), fpm(dzc), s.N, s.C, s.P,
                                              region(0).p, region(0).n, st, s.Cp), "slak_scale_residual_backward_ld");
-    else
-    check_rc(slak_scale_residual_backward(fp(dout), dout16.defined() ? dout16.data_ptr() : nullptr, dsum.defined() ? fpm(dsum) : nullptr, z.data_ptr(),
-                                          fp(gamma), has_scale ? fp(*sample_scale) : nullptr, dz.data_ptr(), fpm(dgamma), fpm(dzc), s.N, s.C, s.P,
-                                          region(0).p, region(0).n, st), "slak_scale_residual_backward");
     Tensor dshortcut = dsum.defined() ? dsum : dout;
     if (shortcut_bf16) dshortcut = dshortcut.to(at::kBFloat16);
     // the MLP's data path: dz -> dact -> (GELU') dy1 (+ pwconv1's bias gradient) -> dt
@@ -412,12 +400,8 @@ std::vector<Tensor> block_backward(const Tensor& x16, const Tensor& wv, const Te
     } else dt_ = at::mm(dy1, w1b);
     // permute + LayerNorm
     Tensor ds = at::empty_like(sum), dlnw = gd.take(G_LNW, {s.C}, f32), dlnb = gd.take(G_LNB, {s.C}, f32);
-    if (pitched)
     check_rc(slak_ln_nchw_to_nhwc_backward_ld(dt_.data_ptr(), sum.data_ptr(), fp(lnw), fp(mean), fp(rstd), ds.data_ptr(), fpm(dlnw), fpm(dlnb), s.N, s.C, s.P,
                                               region(2).p, region(2).n, st, s.Cp), "slak_ln_nchw_to_nhwc_backward_ld");
-    else
-    check_rc(slak_ln_nchw_to_nhwc_backward(dt_.data_ptr(), sum.data_ptr(), fp(lnw), fp(mean), fp(rstd), ds.data_ptr(), fpm(dlnw), fpm(dlnb), s.N, s.C, s.P,
-                                           region(2).p, region(2).n, st), "slak_ln_nchw_to_nhwc_backward");
     // SyncBatchNorm: the backward sums and their all-reduce go out FIRST (asynchronously); the weight gradients below do not depend on them
     const float* gam[3] = {fp(bn_gamma[0]), fp(bn_gamma[1]), fp(bn_gamma[2])};
     Tensor bcoef = at::empty({s.C * 9}, f32);

@@ -50,6 +50,32 @@ def test_pitched_entry_points_refuse_bad_pitches(L, C, ldc):
     assert L.slak_scale_residual_backward_ld(p, None, None, p, p, None, p, p, p, N, C, P, p, 1 << 30, None, ldc) == _lib.ERR_UNSUPPORTED
 
 
+# C = 98: the family query answers TILE for ldc == C, so the pitched call must get as far as the workspace check; 249, 5: ldc == C needs an even C;
+# 96, 1024: multiples of 8, which both rules always took; 1026: above the limit
+@pytest.mark.parametrize("C,P,want", [(98, 400, 3), (249, 49, 2), (5, 9, 2), (96, 196, 3), (1024, 49, 3), (1026, 49, 2)])
+def test_pitch_equal_to_c_gets_the_status_of_the_plain_entry_point(L, C, P, want):
+    """One argument rule: with ldc == C the four `_ld` entry points return what the plain ones return (want: 3 = SLAK_ERR_WORKSPACE behind an
+    accepted shape, 2 = SLAK_ERR_UNSUPPORTED), and the family query agrees.  Host code only: a 16-byte workspace stops every accepted call."""
+    from slak_amd import _lib
+    assert want in (3, _lib.ERR_UNSUPPORTED)
+    buf = ctypes.create_string_buffer(64)                    # never dereferenced
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    N = 2
+    bwd = ((L.slak_ln_nchw_to_nhwc_backward, L.slak_ln_nchw_to_nhwc_backward_ld, (p, p, p, p, p, p, p, p, N, C, P, p, 16, None)),
+           (L.slak_scale_residual_backward, L.slak_scale_residual_backward_ld, (p, None, None, p, p, None, p, p, p, N, C, P, p, 16, None)))
+    for plain, ld, args in bwd:
+        assert plain(*args) == want and ld(*args, C) == want
+    # the forward ops have no workspace: only a refusal can be asked for without a device (an unknown shortcut dtype refuses an accepted shape)
+    if want == _lib.ERR_UNSUPPORTED:
+        assert L.slak_ln_nchw_to_nhwc_forward(p, p, p, p, p, p, N, C, P, 1e-6, None) == want
+        assert L.slak_ln_nchw_to_nhwc_forward_ld(p, p, p, p, p, p, N, C, P, 1e-6, None, C) == want
+    for sdt in ((_lib.SLAK_F32, 99) if want == _lib.ERR_UNSUPPORTED else (99,)):
+        assert L.slak_scale_residual_forward(p, sdt, p, p, None, p, None, N, C, P, None) == _lib.ERR_UNSUPPORTED
+        assert L.slak_scale_residual_forward_ld(p, sdt, p, p, None, p, None, N, C, P, None, C) == _lib.ERR_UNSUPPORTED
+    for op in range(4):
+        assert (L.slak_block_tail_family(op, _lib.SLAK_F32, N, C, P, C) != 0) == (want == 3)
+
+
 def test_pitched_entry_points_check_pointers_and_workspace(L):
     from slak_amd import _lib
     buf = ctypes.create_string_buffer(64)

@@ -10,79 +10,14 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tail_calls import NAN, _close, _ln_bwd_ld, _ln_fwd_ld, _pitched, _sr_bwd_ld, _sr_fwd_ld, _st
+
 pytestmark = pytest.mark.gpu
 
-NAN = float("nan")
-# (N, C, H, W, ldc): tiny C, the two odd stages on 7 x 7 / 14 x 14 / a plane that is no multiple of 4, the widest odd C, the two even width-1.3 stages
+# (N, C, H, W, ldc): tiny C, the two odd stages on 7 x 7 / 14 x 14 / a plane that is no multiple of 4, the widest odd C, the two even width-1.3 stages,
+# an odd C whose four ops all run the pitched LDS-tile kernels (P % 4 == 0 and != 0)
 LD_SHAPES = [(2, 5, 3, 3, 64), (2, 249, 7, 7, 256), (3, 249, 14, 14, 256), (2, 499, 7, 7, 512), (2, 499, 4, 6, 512), (1, 1023, 5, 3, 1024),
-             (2, 124, 8, 8, 128), (2, 998, 7, 7, 1024)]
-
-
-def _close(a, b, rel, what):
-    a, b = a.double(), b.double()
-    err = (a - b).abs().max().item()
-    scale = max(1e-6, b.abs().max().item())
-    assert err <= rel * scale, "%s: err %.3e vs scale %.3e" % (what, err, scale)
-
-
-def _st(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _ws(L, N, ldc, P, dev):
-    nb = int(L.slak_block_tail_workspace_bytes(N, ldc, P))
-    return torch.empty(nb, dtype=torch.uint8, device=dev), nb
-
-
-def _pitched(t, ldc, fill):
-    """(..., C) -> (..., ldc) with `fill` in the pad columns"""
-    out = torch.full(t.shape[:-1] + (ldc,), fill, dtype=t.dtype, device=t.device)
-    out[..., :t.shape[-1]] = t
-    return out
-
-
-def _ln_fwd_ld(L, x, w, b, ldc, eps=1e-6):
-    from slak_amd import _lib
-    N, C, H, W = x.shape
-    y = torch.full((N, H, W, ldc), NAN, dtype=torch.bfloat16, device=x.device)
-    mean = torch.full((N, H * W), NAN, device=x.device); rstd = torch.full((N, H * W), NAN, device=x.device)
-    _lib.check(L.slak_ln_nchw_to_nhwc_forward_ld(x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                                 N, C, H * W, eps, _st(x.device), ldc), "ln fwd ld")
-    return y, mean, rstd
-
-
-def _ln_bwd_ld(L, g, x, w, mean, rstd, ldc):
-    from slak_amd import _lib
-    N, C, H, W = x.shape
-    dx = torch.full_like(x, NAN); dw = torch.full((C,), NAN, device=x.device); db = torch.full((C,), NAN, device=x.device)
-    ws, nb = _ws(L, N, ldc, H * W, x.device)
-    _lib.check(L.slak_ln_nchw_to_nhwc_backward_ld(g.data_ptr(), x.data_ptr(), w.data_ptr(), mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(),
-                                                  dw.data_ptr(), db.data_ptr(), N, C, H * W, ws.data_ptr(), nb, _st(x.device), ldc), "ln bwd ld")
-    return dx, dw, db
-
-
-def _sr_fwd_ld(L, sc, z, gamma, scale, ldc, lowp):
-    from slak_amd import _lib
-    N, C, H, W = sc.shape
-    out = torch.full((N, C, H, W), NAN, device=sc.device)
-    out16 = torch.full((N, C, H, W), NAN, dtype=torch.bfloat16, device=sc.device) if lowp else None
-    sdt = _lib.SLAK_F32 if sc.dtype == torch.float32 else _lib.SLAK_BF16
-    _lib.check(L.slak_scale_residual_forward_ld(sc.data_ptr(), sdt, z.data_ptr(), gamma.data_ptr(), scale.data_ptr() if scale is not None else None,
-                                                out.data_ptr(), out16.data_ptr() if lowp else None, N, C, H * W, _st(sc.device), ldc), "sr fwd ld")
-    return out, out16
-
-
-def _sr_bwd_ld(L, dout, d16, z, gamma, scale, ldc):
-    from slak_amd import _lib
-    N, C, H, W = dout.shape
-    dz = torch.full((N, H, W, ldc), NAN, dtype=torch.bfloat16, device=dout.device)
-    dsum = torch.full_like(dout, NAN) if d16 is not None else None
-    dg = torch.full((C,), NAN, device=dout.device); dzc = torch.full((C,), NAN, device=dout.device)
-    ws, nb = _ws(L, N, ldc, H * W, dout.device)
-    _lib.check(L.slak_scale_residual_backward_ld(dout.data_ptr(), d16.data_ptr() if d16 is not None else None, dsum.data_ptr() if dsum is not None else None,
-                                                 z.data_ptr(), gamma.data_ptr(), scale.data_ptr() if scale is not None else None, dz.data_ptr(),
-                                                 dg.data_ptr(), dzc.data_ptr(), N, C, H * W, ws.data_ptr(), nb, _st(dout.device), ldc), "sr bwd ld")
-    return dsum, dz, dg, dzc
+             (2, 124, 8, 8, 128), (2, 998, 7, 7, 1024), (2, 301, 6, 6, 304), (2, 301, 5, 3, 304)]
 
 
 # ---- 1. pitched LayerNorm ------------------------------------------------------------------------------------------------------
@@ -167,7 +102,8 @@ def test_pitched_scale_residual_matches_torch(N, C, H, W, ldc, mode, gpu):
 
 
 # ---- 3. ldc == C is the existing entry point ------------------------------------------------------------------------------------
-@pytest.mark.parametrize("N,C,H,W", [(2, 96, 16, 16), (2, 64, 9, 11), (2, 384, 14, 14), (3, 512, 14, 14)])
+# (the last three: LDS-tile kernels for every op -- one workgroup per tile with C % 8 != 0, the persistent ones with P % 4 == 0 and != 0)
+@pytest.mark.parametrize("N,C,H,W", [(2, 96, 16, 16), (2, 64, 9, 11), (2, 384, 14, 14), (3, 512, 14, 14), (2, 98, 6, 6), (2, 258, 6, 6), (2, 258, 5, 3)])
 def test_pitch_equal_to_c_is_the_plain_entry_point_bit_for_bit(N, C, H, W, gpu):
     from slak_amd import _lib, block_ops
     L = _lib.lib()
@@ -178,7 +114,11 @@ def test_pitch_equal_to_c_is_the_plain_entry_point_bit_for_bit(N, C, H, W, gpu):
     y, mean, rstd = _ln_fwd_ld(L, x, w, b, C)
     y0, mean0, rstd0 = block_ops._ln_fwd_impl(x, w, b, 1e-6)
     assert torch.equal(y, y0) and torch.equal(mean, mean0) and torch.equal(rstd, rstd0)
+    for a_, b_ in zip((y, mean, rstd), _ln_fwd_ld(L, x, w, b, None)):                    # (None: the plain symbol itself)
+        assert torch.equal(a_, b_)
     for a_, b_ in zip(_ln_bwd_ld(L, g, x, w, mean, rstd, C), block_ops._ln_bwd_impl(g, x, w, mean0, rstd0)):
+        assert torch.equal(a_, b_)
+    for a_, b_ in zip(_ln_bwd_ld(L, g, x, w, mean, rstd, C), _ln_bwd_ld(L, g, x, w, mean, rstd, None)):
         assert torch.equal(a_, b_)
     sc = torch.randn(N, C, H, W, device=gpu); z = torch.randn(N, H, W, C, device=gpu).bfloat16(); gamma = torch.randn(C, device=gpu) * 0.3
     scale = (torch.rand(N, device=gpu) > 0.3).float() / 0.7
@@ -187,6 +127,9 @@ def test_pitch_equal_to_c_is_the_plain_entry_point_bit_for_bit(N, C, H, W, gpu):
         for a_, b_ in zip(_sr_fwd_ld(L, sc, z, gamma, scale, C, True), block_ops._scale_residual_fwd(sc, z, gamma, scale, True)):
             assert torch.equal(a_, b_)
         for a_, b_ in zip(_sr_bwd_ld(L, dout, d16, z, gamma, scale, C), block_ops._scale_residual_bwd(z, gamma, scale, sc.dtype, dout, d16)):
+            assert torch.equal(a_, b_)
+        for a_, b_ in zip(_sr_fwd_ld(L, sc, z, gamma, scale, C, True) + _sr_bwd_ld(L, dout, d16, z, gamma, scale, C),
+                          _sr_fwd_ld(L, sc, z, gamma, scale, None, True) + _sr_bwd_ld(L, dout, d16, z, gamma, scale, None)):
             assert torch.equal(a_, b_)
 
 

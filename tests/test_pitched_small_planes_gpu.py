@@ -10,9 +10,10 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tail_calls import NAN, _close, _ln_bwd_ld, _ln_fwd_ld, _pitched, _sr_bwd_ld, _sr_fwd_ld
+
 pytestmark = pytest.mark.gpu
 
-NAN = float("nan")
 LN_FWD, LN_BWD, SR_FWD, SR_BWD = 0, 1, 2, 3
 REG, CHAN, CHAN1 = 2, 3, 4
 # (N, C, H, W, ldc)
@@ -33,74 +34,8 @@ CHAN1_SHAPES = [
 SHAPES = CHAN_SHAPES + CHAN1_SHAPES
 
 
-def _close(a, b, rel, what):
-    a, b = a.double(), b.double()
-    err = (a - b).abs().max().item()
-    scale = max(1e-6, b.abs().max().item())
-    assert err <= rel * scale, "%s: err %.3e vs scale %.3e" % (what, err, scale)
-
-
-def _st(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _ws(L, N, ldc, P, dev):
-    nb = int(L.slak_block_tail_workspace_bytes(N, ldc, P))
-    return torch.empty(nb, dtype=torch.uint8, device=dev), nb
-
-
-def _pitched(t, ldc, fill):
-    out = torch.full(t.shape[:-1] + (ldc,), fill, dtype=t.dtype, device=t.device)
-    out[..., :t.shape[-1]] = t
-    return out
-
-
 def _family(L, op, dt, N, C, P, ldc):
     return int(L.slak_block_tail_family(op, dt, N, C, P, ldc))
-
-
-def _ln_fwd_ld(L, x, w, b, ldc, eps=1e-6):
-    from slak_amd import _lib
-    N, C, H, W = x.shape
-    y = torch.full((N, H, W, ldc), NAN, dtype=torch.bfloat16, device=x.device)
-    mean = torch.full((N, H * W), NAN, device=x.device); rstd = torch.full((N, H * W), NAN, device=x.device)
-    _lib.check(L.slak_ln_nchw_to_nhwc_forward_ld(x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                                 N, C, H * W, eps, _st(x.device), ldc), "ln fwd ld")
-    return y, mean, rstd
-
-
-def _ln_bwd_ld(L, g, x, w, mean, rstd, ldc):
-    from slak_amd import _lib
-    N, C, H, W = x.shape
-    dx = torch.full_like(x, NAN); dw = torch.full((C,), NAN, device=x.device); db = torch.full((C,), NAN, device=x.device)
-    ws, nb = _ws(L, N, ldc, H * W, x.device)
-    _lib.check(L.slak_ln_nchw_to_nhwc_backward_ld(g.data_ptr(), x.data_ptr(), w.data_ptr(), mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(),
-                                                  dw.data_ptr(), db.data_ptr(), N, C, H * W, ws.data_ptr(), nb, _st(x.device), ldc), "ln bwd ld")
-    return dx, dw, db
-
-
-def _sr_fwd_ld(L, sc, z, gamma, scale, ldc, lowp):
-    from slak_amd import _lib
-    N, C, H, W = sc.shape
-    out = torch.full((N, C, H, W), NAN, device=sc.device)
-    out16 = torch.full((N, C, H, W), NAN, dtype=torch.bfloat16, device=sc.device) if lowp else None
-    sdt = _lib.SLAK_F32 if sc.dtype == torch.float32 else _lib.SLAK_BF16
-    _lib.check(L.slak_scale_residual_forward_ld(sc.data_ptr(), sdt, z.data_ptr(), gamma.data_ptr(), scale.data_ptr() if scale is not None else None,
-                                                out.data_ptr(), out16.data_ptr() if lowp else None, N, C, H * W, _st(sc.device), ldc), "sr fwd ld")
-    return out, out16
-
-
-def _sr_bwd_ld(L, dout, d16, z, gamma, scale, ldc):
-    from slak_amd import _lib
-    N, C, H, W = dout.shape
-    dz = torch.full((N, H, W, ldc), NAN, dtype=torch.bfloat16, device=dout.device)
-    dsum = torch.full_like(dout, NAN) if d16 is not None else None
-    dg = torch.full((C,), NAN, device=dout.device); dzc = torch.full((C,), NAN, device=dout.device)
-    ws, nb = _ws(L, N, ldc, H * W, dout.device)
-    _lib.check(L.slak_scale_residual_backward_ld(dout.data_ptr(), d16.data_ptr() if d16 is not None else None, dsum.data_ptr() if dsum is not None else None,
-                                                 z.data_ptr(), gamma.data_ptr(), scale.data_ptr() if scale is not None else None, dz.data_ptr(),
-                                                 dg.data_ptr(), dzc.data_ptr(), N, C, H * W, ws.data_ptr(), nb, _st(dout.device), ldc), "sr bwd ld")
-    return dsum, dz, dg, dzc
 
 
 @pytest.mark.parametrize("N,C,H,W,ldc", SHAPES)
