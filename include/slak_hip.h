@@ -59,7 +59,7 @@ const char* slak_last_hip_error(void);      /* text of the last HIP error seen b
 /* ABI version: bumped whenever an entry point's argument list or meaning changes (round 5: 5).  A host module compiled against this header
  * (slak_amd/pybind, *.cpp) records the value it saw and refuses to load on a library that reports another one: a stale module would call raw-pointer
  * entry points with a changed argument list -- silent corruption, not an error. */
-#define SLAK_ABI_VERSION 8
+#define SLAK_ABI_VERSION 9
 int slak_version(void);                     /* == SLAK_ABI_VERSION of the header the library was built from */
 int slak_device_info(int* cu_count, int* lds_bytes_per_cu, char* arch_name, size_t arch_name_len);
 int slak_set_conv_algo(int algo);           /* process-wide override of the AUTO choice */
@@ -412,6 +412,36 @@ int slak_linear_wgrad(const void* x1_bf16, const void* x2_bf16, float* d, int M,
 size_t slak_gelu_bwd_workspace_bytes(int rows, int cols);
 int slak_gelu_backward_bias(const void* dact_bf16, const void* y1_bf16, void* dy1_bf16, float* dbias, int rows, int cols,
                             void* workspace, size_t workspace_bytes, void* stream);
+
+/* Which launch runs each step of a block's pointwise MLP (models/SLaK.py:158-160: pwconv1 -> GELU -> pwconv2, its data gradient and its two weight
+ * gradients) on M rows of Cp channels, C4 = rows of W1 (4 Cp).  The ONE place where the ladder is written: every step takes the first rung, in the
+ * order listed, whose slak_linear_*_supported query says yes and whose kernel family `allow` admits; LIBRARY (the caller's GEMM) ends every ladder.
+ * Pure host code, built from the *_supported / *_workspace_bytes queries above and nothing else, so a launch never refuses what the plan chose.
+ * Both callers (slak_amd/block_ops.py, slak_amd/pybind/block_runner.cpp) switch on the answer.
+ *   pw1   pwconv1 + GELU:      FUSED   slak_linear_mlp_fwd (pwconv2 is in the same launch: pw2 is not looked at)
+ *                              NT      slak_linear_nt with gelu_out
+ *                              GEMM    slak_linear_gemm, SLAK_EPI_GELU
+ *                              LIBRARY the caller's GEMM, then GELU
+ *   pw2   pwconv2:             NT slak_linear_nt | LIBRARY
+ *   dy1   dz W2, GELU', db1:   FUSED_DT slak_linear_nt_gelu_bwd_dt (dt = dy1 W1 is in the same launch: dt is not looked at; needs W1^T packed by slak_pack_w1t_fragments)
+ *                              FUSED   slak_linear_nt_gelu_bwd
+ *                              GEMM    slak_linear_gemm, SLAK_EPI_DGELU
+ *                              NT      slak_linear_nt, then slak_gelu_backward_bias
+ *                              LIBRARY the caller's GEMM, then slak_gelu_backward_bias
+ *   dt    dy1 W1:              NT slak_linear_nt | LIBRARY
+ *   dw1, dw2  dy1^T t, dz^T a: KERNEL slak_linear_wgrad | LIBRARY: the M rows as `splits` batches of a batched GEMM, the partial products added in fp32
+ *                              (splits = max(1, M / rows) lowered until it divides M; 1: one plain GEMM; rows = SLAK_SPLITK_ROWS in the environment,
+ *                              read once, default 6272, <= 0: never split)
+ *   ws_*  workspace bytes of the CHOSEN launch of dy1 (with slak_gelu_backward_bias's on the NT / LIBRARY rungs), dw1 and dw2; 0: none.
+ * allow: SLAK_MLP_ALLOW_SKINNY (linear_skinny.hip: FUSED, FUSED_DT, NT) | _GEMM (linear_gemm.hip) | _WGRAD (linear_wgrad.hip); 0 is LIBRARY everywhere
+ * (what a caller whose operands are not contiguous bf16 device tensors asks for).  SLAK_ERR_INVALID_ARG: plan == NULL or a dimension <= 0. */
+enum { SLAK_MLP_LIBRARY = 0, SLAK_MLP_NT = 1, SLAK_MLP_GEMM = 2, SLAK_MLP_FUSED = 3, SLAK_MLP_FUSED_DT = 4, SLAK_MLP_KERNEL = 5 };
+enum { SLAK_MLP_ALLOW_SKINNY = 1, SLAK_MLP_ALLOW_GEMM = 2, SLAK_MLP_ALLOW_WGRAD = 4, SLAK_MLP_ALLOW_ALL = 7 };
+typedef struct slak_mlp_plan {
+    int pw1, pw2, dy1, dt, dw1, dw2, splits;
+    size_t ws_dy1, ws_dw1, ws_dw2;
+} slak_mlp_plan_t;
+int slak_mlp_plan(int M, int C4, int Cp, unsigned allow, slak_mlp_plan_t* plan);
 
 /* channels_first LayerNorm of the stem / downsample layers (models/SLaK.py:192-203, :256-261): y[n,c,p] = LN_C(x[n,:,p])*w + b, NCHW in
  * and out; x/y/g/dx fp32 or bf16 (dx has the dtype of x). */

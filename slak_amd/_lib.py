@@ -50,6 +50,10 @@ class MixupRecord(ctypes.Structure):
                 ("yl", ctypes.c_int), ("yh", ctypes.c_int), ("xl", ctypes.c_int), ("xh", ctypes.c_int)]
 
 
+class MlpPlan(ctypes.Structure):                                     # slak_mlp_plan_t: the rung of every step of a block's pointwise MLP (include/slak_hip.h)
+    _fields_ = [(n, ctypes.c_int) for n in ("pw1", "pw2", "dy1", "dt", "dw1", "dw2", "splits")] + [(n, ctypes.c_size_t) for n in ("ws_dy1", "ws_dw1", "ws_dw2")]
+
+
 # name -> (restype, argtypes): every symbol include/slak_hip.h declares (tests/test_boundary.py checks this)
 _vp, _i, _sz, _d = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_double
 _CONV = [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]
@@ -154,6 +158,7 @@ SIGNATURES = {
     "slak_linear_wgrad_supported": (_i, [_i, _i, _i]),
     "slak_linear_wgrad_workspace_bytes": (_sz, [_i, _i, _i]),
     "slak_linear_wgrad": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
+    "slak_mlp_plan": (_i, [_i, _i, _i, ctypes.c_uint, ctypes.POINTER(MlpPlan)]),   # (M, C4, Cp, allow, plan); host only
     "slak_scale_residual_forward": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "slak_scale_residual_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
     "slak_ln_nchw_to_nhwc_forward_ld": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, ctypes.c_float, _vp, _i]),
@@ -180,6 +185,10 @@ MIXUP_NONE, MIXUP_MIX, MIXUP_CUTMIX = 0, 1, 2                      # slak_mixup_
 TAIL_LN_FWD, TAIL_LN_BWD, TAIL_SR_FWD, TAIL_SR_BWD = 0, 1, 2, 3
 TAIL_FAMILY_NONE, TAIL_FAMILY_TILE, TAIL_FAMILY_REG, TAIL_FAMILY_CHAN, TAIL_FAMILY_CHAN1 = 0, 1, 2, 3, 4
 TAIL_FAMILY_NAMES = ("none", "tile", "reg", "chan", "chan1")
+# slak_mlp_plan: rungs and the `allow` mask (include/slak_hip.h)
+MLP_LIBRARY, MLP_NT, MLP_GEMM, MLP_FUSED, MLP_FUSED_DT, MLP_KERNEL = 0, 1, 2, 3, 4, 5
+MLP_RUNG_NAMES = ("library", "nt", "gemm", "fused", "fused_dt", "kernel")
+MLP_ALLOW_SKINNY, MLP_ALLOW_GEMM, MLP_ALLOW_WGRAD, MLP_ALLOW_ALL = 1, 2, 4, 7
 
 
 def lib():

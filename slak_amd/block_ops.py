@@ -419,15 +419,9 @@ class _LinearSplitK(torch.autograd.Function):
         x, wb = ctx.saved_tensors
         x2 = x.reshape(-1, x.shape[-1]); dy2 = dy.reshape(-1, dy.shape[-1])
         dx = torch.mm(dy2, wb).view_as(x)
-        M = x2.shape[0]
-        S = max(1, M // 6272)
-        while S > 1 and M % S:
-            S -= 1
-        dw = linear_wgrad(dy2.contiguous(), x2.contiguous()) if dy2.dtype == torch.bfloat16 and x2.dtype == torch.bfloat16 else None
-        if dw is None and S > 1:
-            dw = torch.bmm(dy2.view(S, M // S, -1).transpose(1, 2), x2.view(S, M // S, -1)).sum(0, dtype=torch.float32)
-        elif dw is None:
-            dw = torch.mm(dy2.t(), x2).float()
+        dy2, x2 = dy2.contiguous(), x2.contiguous()
+        plan = _mlp_plan(x2.shape[0], dy2.shape[1], x2.shape[1], _mlp_allow(dy2, x2))     # dW = dy^T x is the MLP's dW1 with (C4, Cp) = (out, in) features
+        dw = _mlp_wgrad(dy2, x2, plan.dw1, plan.splits)
         db = dy2.sum(0, dtype=torch.float32) if ctx.has_bias else None
         return dx, dw, db
 
@@ -950,7 +944,6 @@ def downsample_ln_conv(x, ln_w, ln_b, conv_w, conv_b, eps=1e-6):
 
 
 # ------------------------------------------------------------------------------------------------------------------
-import os as _os
 import weakref as _weakref
 
 # bf16 copies of the fp32 master weights the pointwise GEMMs read, refreshed in ONE multi-tensor launch per optimizer step
@@ -1133,9 +1126,6 @@ def w1_fragments(w1t):
     return w1p
 
 
-_SPLITK_ROWS = int(_os.environ.get("SLAK_SPLITK_ROWS", "6272"))     # rows per split of the weight-gradient GEMMs (0: one plain GEMM)
-
-
 use_skinny_linear = os.environ.get("SLAK_SKINNY_LINEAR", "1") != "0"      # the streaming kernels of csrc/linear_skinny.hip for the stage-1 pointwise convs (-0.16 ms per SLaK-T step same-box vs the TUNED library GEMMs); 0: library GEMMs everywhere
 
 
@@ -1157,14 +1147,6 @@ def linear_wgrad(dy, x):
         _lib.check(L.slak_linear_wgrad(dy.data_ptr(), x.data_ptr(), d.data_ptr(), M, N1, N2, ws.data_ptr() if ws is not None else None, nb,
                                        _stream(dy.device)), "slak_linear_wgrad")
     return d
-
-
-def linear_nt_covers(x, N, gelu=False):
-    """Whether slak_linear_nt takes x (..., K) bf16 against a weight with N output features."""
-    if not (use_skinny_linear and x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous()):
-        return False
-    K = x.shape[-1]
-    return bool(_lib.lib().slak_linear_nt_supported(x.numel() // K, N, K, 1 if gelu else 0))
 
 
 def linear_nt(x, wt, bias=None, gelu=False):
@@ -1227,54 +1209,75 @@ def linear_gemm_dgelu(dz2, w2t, y12):
     return dy1, db1
 
 
+# The MLP's kernel ladder is written once, in the library (slak_mlp_plan, include/slak_hip.h): _mlp_fwd, _mlp_bwd_data and _mlp_bwd_weights check their
+# operands once, ask for the plan and switch on it -- as slak_amd/pybind/block_runner.cpp does on the same plan.  The one-launch wrappers above answer
+# None where they decline; declining what the plan chose is an error.
+_mlp_plan_cache = {}
+
+
+def _mlp_allow(*operands):
+    """slak_mlp_plan's `allow` mask: the three kernel-family switches above -- or 0, the library GEMMs on every rung, when an operand is not a
+    contiguous bfloat16 HIP tensor (None, a missing bias, included)."""
+    if not all(t is not None and t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous() for t in operands):
+        return 0
+    return ((_lib.MLP_ALLOW_SKINNY if use_skinny_linear else 0) | (_lib.MLP_ALLOW_GEMM if use_linear_gemm else 0) |
+            (_lib.MLP_ALLOW_WGRAD if use_linear_wgrad else 0))
+
+
+def _mlp_plan(M, C4, Cp, allow):
+    """slak_mlp_plan's answer for M rows of Cp channels (C4: rows of W1), asked once per (shape, allow)."""
+    key = (M, C4, Cp, allow)
+    plan = _mlp_plan_cache.get(key)
+    if plan is None:
+        plan = _lib.MlpPlan()
+        _lib.check(_lib.lib().slak_mlp_plan(M, C4, Cp, allow, ctypes.byref(plan)), "slak_mlp_plan")
+        _mlp_plan_cache[key] = plan
+    return plan
+
+
+def _chosen(r, what):
+    if r is None:
+        raise _lib.SlakHipError("%s declined a launch that slak_mlp_plan chose" % what)
+    return r
+
+
 def _mlp_fwd(t, w1, b1, w2, b2, cast=None):
-    """cast: parameter -> the bf16 operand the GEMMs read (default lowp_param; a pitched block hands its zero-padded copies)."""
+    """cast: parameter -> the bf16 operand the GEMMs read (default lowp_param; a pitched block hands its zero-padded copies).
+    SLaK's pointwise layers always have biases: a call with b1 or b2 missing runs the library GEMMs (the LIBRARY rungs)."""
     F = torch.nn.functional
     cast = lowp_param if cast is None else cast
-    w1b, w2b = cast(w1), cast(w2)
-    L = _lib.lib()
+    w1b, w2b, bb1, bb2 = (None if p is None else cast(p) for p in (w1, w2, b1, b2))
     C, C4 = w1b.shape[1], w1b.shape[0]
     M = t.numel() // C
-    if use_skinny_linear and t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous() and w1b.dtype == torch.bfloat16 and w1b.is_contiguous() and \
-            w2b.is_contiguous() and b1 is not None and b2 is not None and L.slak_linear_mlp_fwd_supported(M, C, C4):
-        # stage 1: pwconv1, GELU and pwconv2 in ONE pass (W2 lives in the waves' registers; a is not read back)
+    plan = _mlp_plan(M, C4, C, _mlp_allow(t, w1b, w2b, bb1, bb2))
+    if plan.pw1 == _lib.MLP_FUSED:                          # stage 1: pwconv1, GELU and pwconv2 in ONE pass (W2 lives in the waves' registers; a is not read back)
         y1 = torch.empty(t.shape[:-1] + (C4,), dtype=torch.bfloat16, device=t.device)
         a = torch.empty_like(y1)
         z = torch.empty(t.shape[:-1] + (C,), dtype=torch.bfloat16, device=t.device)
-        bb1, bb2 = cast(b1), cast(b2)
         with _on(t.device):
-            _lib.check(L.slak_linear_mlp_fwd(t.data_ptr(), w1b.data_ptr(), bb1.data_ptr(), w2b.data_ptr(), bb2.data_ptr(), y1.data_ptr(), a.data_ptr(),
-                                             z.data_ptr(), M, C, C4, _stream(t.device)), "slak_linear_mlp_fwd")
+            _lib.check(_lib.lib().slak_linear_mlp_fwd(t.data_ptr(), w1b.data_ptr(), bb1.data_ptr(), w2b.data_ptr(), bb2.data_ptr(), y1.data_ptr(), a.data_ptr(),
+                                                      z.data_ptr(), M, C, C4, _stream(t.device)), "slak_linear_mlp_fwd")
         return z, (t, w1b, y1, a, w2b)
-    r = linear_nt(t, w1b, cast(b1), gelu=True)            # pwconv1 + GELU in one streaming pass on the large maps
-    if r is None and b1 is not None:
-        r = linear_gemm_gelu(t, w1b, cast(b1))            # stages 2-3: the GEMM with bias, rounding and GELU in its epilogue (y1 AND a in one launch)
-    if r is not None:
-        y1, a = r
+    if plan.pw1 == _lib.MLP_NT:                             # pwconv1 + GELU in one streaming pass on the large maps
+        y1, a = _chosen(linear_nt(t, w1b, bb1, gelu=True), "linear_nt")
+    elif plan.pw1 == _lib.MLP_GEMM:                         # stages 2-3: the GEMM with bias, rounding and GELU in its epilogue (y1 AND a in one launch)
+        y1, a = _chosen(linear_gemm_gelu(t, w1b, bb1), "linear_gemm_gelu")
     else:
-        y1 = F.linear(t, w1b, cast(b1))
+        y1 = F.linear(t, w1b, bb1)
         a = F.gelu(y1)
-    z = linear_nt(a, w2b, cast(b2))
-    if z is None:
-        z = F.linear(a, w2b, cast(b2))
+    z = _chosen(linear_nt(a, w2b, bb2), "linear_nt") if plan.pw2 == _lib.MLP_NT else F.linear(a, w2b, bb2)
     return z, (t, w1b, y1, a, w2b)
 
 
-def _mlp_wgrad(dy, x):
-    """dW = dy^T x (fp32) for the pointwise Linear layers: slak_linear_wgrad where it covers the shape, else the library's split-K batched GEMM."""
-    d = linear_wgrad(dy, x)
-    if d is not None:
-        return d
-    M = dy.shape[0]
-    S = max(1, M // _SPLITK_ROWS) if _SPLITK_ROWS > 0 else 1
-    while S > 1 and M % S:
-        S -= 1
+def _mlp_wgrad(dy, x, rung, splits):
+    """dW = dy^T x (fp32) for the pointwise Linear layers on slak_mlp_plan's rung: slak_linear_wgrad, or the library's batched GEMM over `splits` slices of
+    the rows with the partial products added in fp32 (splits == 1: one plain GEMM)."""
+    if rung == _lib.MLP_KERNEL:
+        return _chosen(linear_wgrad(dy, x), "linear_wgrad")
+    M, S = dy.shape[0], splits
     if S > 1:
         return torch.bmm(dy.view(S, M // S, -1).transpose(1, 2), x.view(S, M // S, -1)).sum(0, dtype=torch.float32)
     return torch.mm(dy.t(), x).float()
-
-
-_gelu_ws_cache = {}
 
 
 def _mlp_bwd_data(saved, dz, wts=None):
@@ -1285,62 +1288,46 @@ def _mlp_bwd_data(saved, dz, wts=None):
     w2t_of = (lambda: wts[1]) if wts is not None else (lambda: w2b.t().contiguous())
     dz2 = dz.reshape(-1, dz.shape[-1])
     y12 = y1.reshape(-1, y1.shape[-1])
-    M = dz2.shape[0]
-    dact = None
-    L = _lib.lib()
-    N4 = w2b.shape[1]
-    if use_skinny_linear and dz2.is_contiguous() and y12.is_contiguous() and dz2.dtype == torch.bfloat16 and w2b.dtype == torch.bfloat16 and \
-            L.slak_linear_nt_gelu_bwd_supported(M, N4, dz2.shape[1]):
-        # stage 1: dz @ W2, GELU' and pwconv1's bias gradient in ONE pass (dact never reaches HBM)
-        dy1 = torch.empty((M, N4), dtype=torch.bfloat16, device=dz2.device)
-        db1 = torch.empty(N4, dtype=torch.float32, device=dz2.device)
+    M, C = dz2.shape
+    C4 = w2b.shape[1]
+    L, dev = _lib.lib(), dz2.device
+    plan = _mlp_plan(M, C4, C, _mlp_allow(dz2, y12, w1b, w2b))
+    if plan.dy1 in (_lib.MLP_FUSED_DT, _lib.MLP_FUSED):    # stage 1: dz @ W2, GELU' and pwconv1's bias gradient in ONE pass (dact never reaches HBM)
+        dy1 = torch.empty((M, C4), dtype=torch.bfloat16, device=dev)
+        db1 = torch.empty(C4, dtype=torch.float32, device=dev)
         w2t = w2t_of()
-        ws, nb = _workspace(int(L.slak_linear_nt_gelu_bwd_workspace_bytes(M, N4, dz2.shape[1])), dz2.device)
-        if L.slak_linear_nt_gelu_bwd_dt_supported(M, N4, dz2.shape[1]):
-            # ... and dt = dy1 @ W1 from the dy1 tiles while they are on chip (no second launch, dy1 is not read back)
+        ws, nb = _workspace(plan.ws_dy1, dev)
+        if plan.dy1 == _lib.MLP_FUSED_DT:                   # ... and dt = dy1 @ W1 from the dy1 tiles while they are on chip (no second launch, dy1 is not read back)
             w1p = w1_fragments(w1t_of())
-            dt = torch.empty((M, dz2.shape[1]), dtype=torch.bfloat16, device=dz2.device)
-            with _on(dz2.device):
+            dt = torch.empty((M, C), dtype=torch.bfloat16, device=dev)
+            with _on(dev):
                 _lib.check(L.slak_linear_nt_gelu_bwd_dt(dz2.data_ptr(), w2t.data_ptr(), y12.data_ptr(), w1p.data_ptr(), dy1.data_ptr(), dt.data_ptr(), db1.data_ptr(),
-                                                        M, N4, dz2.shape[1], ws.data_ptr(), nb, _stream(dz2.device)), "slak_linear_nt_gelu_bwd_dt")
+                                                        M, C4, C, ws.data_ptr(), nb, _stream(dev)), "slak_linear_nt_gelu_bwd_dt")
             return dt.view_as(t), dy1, db1
-        with _on(dz2.device):
-            _lib.check(L.slak_linear_nt_gelu_bwd(dz2.data_ptr(), w2t.data_ptr(), y12.data_ptr(), dy1.data_ptr(), db1.data_ptr(), M, N4, dz2.shape[1],
-                                                 ws.data_ptr(), nb, _stream(dz2.device)), "slak_linear_nt_gelu_bwd")
-        dt = linear_nt(dy1, w1t_of()) if linear_nt_covers(dy1, w1b.shape[1]) else None
-        dt = (dt if dt is not None else torch.mm(dy1, w1b)).view_as(t)
-        return dt, dy1, db1
-    r = linear_gemm_dgelu(dz2, w2t_of(), y12) if (dz2.is_contiguous() and y12.is_contiguous()) else None
-    if r is not None:                                            # stages 2-3: dz @ W2 with GELU' and pwconv1's bias gradient in the GEMM's epilogue
-        dy1, db1 = r
-        dt = linear_nt(dy1, w1t_of()) if linear_nt_covers(dy1, w1b.shape[1]) else None
-        dt = (dt if dt is not None else torch.mm(dy1, w1b)).view_as(t)
-        return dt, dy1, db1
-    if linear_nt_covers(dz2, w2b.shape[1]):
-        dact = linear_nt(dz2, w2t_of())              # dz @ W2: NT against the (small) transposed weight
-    if dact is None:
-        dact = torch.mm(dz2, w2b)
-    dy1 = torch.empty_like(dact)
-    db1 = torch.empty(dact.shape[1], dtype=torch.float32, device=dact.device)
-    key = (M, dact.shape[1])
-    nbw = _gelu_ws_cache.get(key)
-    if nbw is None:
-        nbw = _gelu_ws_cache[key] = int(L.slak_gelu_bwd_workspace_bytes(M, dact.shape[1]))
-    ws, nb = _workspace(nbw, dact.device)
-    with _on(dact.device):
-        _lib.check(L.slak_gelu_backward_bias(dact.data_ptr(), y12.data_ptr(), dy1.data_ptr(), db1.data_ptr(), M, dact.shape[1],
-                                             ws.data_ptr() if ws is not None else None, nb, _stream(dact.device)), "slak_gelu_backward_bias")
-    dt = linear_nt(dy1, w1t_of()) if linear_nt_covers(dy1, w1b.shape[1]) else None
-    dt = (dt if dt is not None else torch.mm(dy1, w1b)).view_as(t)
-    return dt, dy1, db1
+        with _on(dev):
+            _lib.check(L.slak_linear_nt_gelu_bwd(dz2.data_ptr(), w2t.data_ptr(), y12.data_ptr(), dy1.data_ptr(), db1.data_ptr(), M, C4, C,
+                                                 ws.data_ptr(), nb, _stream(dev)), "slak_linear_nt_gelu_bwd")
+    elif plan.dy1 == _lib.MLP_GEMM:                         # stages 2-3: dz @ W2 with GELU' and pwconv1's bias gradient in the GEMM's epilogue
+        dy1, db1 = _chosen(linear_gemm_dgelu(dz2, w2t_of(), y12), "linear_gemm_dgelu")
+    else:                                                   # dz @ W2 (NT: against the small transposed weight), then GELU' and the bias gradient as a pass of their own
+        dact = _chosen(linear_nt(dz2, w2t_of()), "linear_nt") if plan.dy1 == _lib.MLP_NT else torch.mm(dz2, w2b)
+        dy1 = torch.empty_like(dact)
+        db1 = torch.empty(C4, dtype=torch.float32, device=dev)
+        ws, nb = _workspace(plan.ws_dy1, dev)
+        with _on(dev):
+            _lib.check(L.slak_gelu_backward_bias(dact.data_ptr(), y12.data_ptr(), dy1.data_ptr(), db1.data_ptr(), M, C4,
+                                                 ws.data_ptr() if ws is not None else None, nb, _stream(dev)), "slak_gelu_backward_bias")
+    dt = _chosen(linear_nt(dy1, w1t_of()), "linear_nt") if plan.dt == _lib.MLP_NT else torch.mm(dy1, w1b)
+    return dt.view_as(t), dy1, db1
 
 
 def _mlp_bwd_weights(saved, dz, dy1):
     """The two pointwise weight gradients (they feed nothing else of the block's backward) -> (dw1, dw2)"""
     t, w1b, y1, a, w2b = saved
-    dz2 = dz.reshape(-1, dz.shape[-1])
-    dw2 = _mlp_wgrad(dz2, a.reshape(-1, a.shape[-1]))
-    dw1 = _mlp_wgrad(dy1, t.reshape(-1, t.shape[-1]))
+    dz2, a2, t2 = dz.reshape(-1, dz.shape[-1]), a.reshape(-1, a.shape[-1]), t.reshape(-1, t.shape[-1])
+    plan = _mlp_plan(dz2.shape[0], a2.shape[1], t2.shape[1], _mlp_allow(dz2, a2, dy1, t2))
+    dw2 = _mlp_wgrad(dz2, a2, plan.dw2, plan.splits)
+    dw1 = _mlp_wgrad(dy1, t2, plan.dw1, plan.splits)
     return dw1, dw2
 
 
@@ -1445,9 +1432,9 @@ _force_bn_exchange = os.environ.get("SLAK_FORCE_BN_EXCHANGE", "0") == "1"   # be
 
 def _runner_switches():
     """The development switches that select paths only the Python sequence knows: with any of them off their default the runner steps aside, so an
-    A/B run measures what its switch says.  Read on every call: a test may flip a switch after the first block has run."""
-    return (use_skinny_linear and use_linear_wgrad and use_linear_gemm and _SPLITK_ROWS == 6272 and fused_tri_backward and fused_tri_wgrad
-            and bn_stats_in_conv and accumulate_dgrad and os.environ.get("SLAK_BLOCK_RUNNER", "1") != "0")
+    A/B run measures what its switch says.  Read on every call: a test may flip a switch after the first block has run.
+    (The MLP's switches are not among them: the runner follows slak_mlp_plan under the same `allow` mask as the Python sequence.)"""
+    return (fused_tri_backward and fused_tri_wgrad and bn_stats_in_conv and accumulate_dgrad and os.environ.get("SLAK_BLOCK_RUNNER", "1") != "0")
 
 
 def _runner():
@@ -1579,9 +1566,10 @@ class _BlockFn(torch.autograd.Function):
                 w1b, bb1b, w2b, bb2b = lowp_param(w1), lowp_param(bb1), lowp_param(w2), lowp_param(bb2)
             group = _bn3_group(bns[0])                                # SyncBatchNorm: the runner calls back for the two statistics exchanges
             exchange = _runner_exchange(group)
+            ctx.mlp_allow = _mlp_allow(w1b, bb1b, w2b, bb2b)         # the backward asks for the same plan
             res = R.block_forward(x, x_lowp, wv, wh, ws, [g1, g2, g3], [b1, b2, b3], [bn.running_mean for bn in bns], [bn.running_var for bn in bns],
                                   float(bns[0].eps), float(bns[0].momentum), True, lnw, lnb, float(eps), w1b, bb1b, w2b, bb2b,
-                                  gamma, sample_scale, bool(emit), exchange, int(ldc))
+                                  gamma, sample_scale, bool(emit), exchange, int(ldc), ctx.mlp_allow)
             if res:                                                   # (empty: the shape has no one-launch path -- the Python sequence knows the fallbacks)
                 out, out16, x16, yv, yh, ys, bnstats, s, t, mean, rstd, y1m, a, z, count_dev = res
                 pool = getattr(bns[0], "_slak_ctr_pool", None)
@@ -1633,11 +1621,12 @@ class _BlockFn(torch.autograd.Function):
         if ctx.runner:
             exchange = _runner_exchange(group)
             w1p = None                                                # stage 1: W1^T in fragment order for the launch that also produces dt
-            if tuple(w1b.shape) == (384, 96) and w1b.dtype == torch.bfloat16 and _lib.lib().slak_linear_nt_gelu_bwd_dt_supported(t.numel() // 96, 384, 96):
+            if _mlp_plan(t.numel() // w1b.shape[1], w1b.shape[0], w1b.shape[1], ctx.mlp_allow).dy1 == _lib.MLP_FUSED_DT:
                 w1p = w1_fragments(w1t if w1t is not None else w1b.t().contiguous())
             res = _runner_mod.block_backward(
                 x16, wv, wh, ws, yv, yh, ys, [g1, g2, g3], bnstats, s, lnw, mean, rstd, t, w1b, y1m, a, w2b, z, gamma, sample_scale, dout, dout16,
-                xdtype == torch.bfloat16, had_lowp, count_dev, exchange, _runner_trace, w1t, w2t, w1p, _grad_destinations(ctx.params), int(w1b.shape[1]))
+                xdtype == torch.bfloat16, had_lowp, count_dev, exchange, _runner_trace, w1t, w2t, w1p, _grad_destinations(ctx.params), int(w1b.shape[1]),
+                ctx.mlp_allow, _bn_bwd_async)
             return (*res, None, None)                                 # dx, dx_lowp, then the sixteen parameter gradients in forward()'s order
         saved = (t, w1b, y1m, a, w2b)
         dshortcut, dz, dgamma, dzc = _scale_residual_bwd(z, gamma, sample_scale, xdtype, dout, dout16)

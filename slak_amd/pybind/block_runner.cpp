@@ -3,7 +3,8 @@
 // pwconv2 -> gamma * + permute + residual, and its backward) as TWO host calls per block and step instead of ~70 ctypes calls, ~25 torch.empty
 // and 4-6 GEMM dispatches made from Python.  Same launches on the same operands in the same order as the Python node: results are bit-identical
 // (tests/test_model_reference_gpu.py::test_block_runner_issues_the_same_launches_as_the_python_node).  Host-only C++ on the C ABI of include/slak_hip.h; tensors are allocated through the torch allocator, kernels
-// go to torch's CURRENT stream, the GEMMs the library does not cover are at::linear / at::mm (hipBLASLt).
+// go to torch's CURRENT stream, the GEMMs the library does not cover are at::linear / at::mm (hipBLASLt).  Which launch runs each step of the pointwise MLP
+// is the library's answer (slak_mlp_plan under the caller's `allow` mask): the Python sequence switches on the same plan.
 //
 // SyncBatchNorm (round 5): with an `exchange` callable (block_ops._sync_bn_all_reduce bound to the process group) the branch BatchNorms run as
 // sums -> exchange -> apply: forward one blocking all-reduce of 6C+1 doubles, backward one all-reduce of 4C floats issued ASYNCHRONOUSLY in front of
@@ -119,11 +120,11 @@ Side& side_of(int dev) {
 
 struct Shape { int N, C, H, W, K, P, M, C4, Cp; };                  // Cp: the row pitch of the NHWC tensors (== C: a plain block); C4: rows of W1 as handed in (4 Cp)
 
-// what the library answers for a block shape, asked once
-struct Plan { bool ok; int rows; size_t ws; bool nt1, nt2, ntd1, ntd2, wg1, wg2, bwd1, gbwd, mlp1, gg1, gg2; size_t off[5], len[5]; };   // off/len: the backward's deferred-reduction regions behind the common scratch
-const Plan& plan_of(const Shape& s) {
+// what the library answers for a block shape and the caller's `allow` mask of MLP kernel families (slak_mlp_plan), asked once
+struct Plan { bool ok; int rows; size_t ws; bool bwd1; slak_mlp_plan_t mlp; size_t off[5], len[5]; };   // off/len: the backward's deferred-reduction regions behind the common scratch
+const Plan& plan_of(const Shape& s, unsigned allow) {
     static std::map<std::vector<int>, Plan> cache;
-    const std::vector<int> key = {s.N, s.C, s.H, s.W, s.K, s.C4, s.Cp};
+    const std::vector<int> key = {s.N, s.C, s.H, s.W, s.K, s.C4, s.Cp, (int)allow};
     std::lock_guard<std::mutex> lk(g_cache_mu);
     auto it = cache.find(key);
     if (it != cache.end()) return it->second;
@@ -132,41 +133,21 @@ const Plan& plan_of(const Shape& s) {
     p.rows = slak_dwconv2d_tri_stats_rows(dt, s.N, s.C, s.H, s.W, s.K);
     const size_t wtri = slak_dwconv2d_tri_filter_workspace_bytes(dt, s.N, s.C, s.H, s.W, s.K);
     p.ok = slak_dwconv2d_tri_supported_op(dt, s.N, s.C, s.H, s.W, s.K, 0) == 1 && slak_dwconv2d_tri_supported_op(dt, s.N, s.C, s.H, s.W, s.K, 1) == 1 &&
-           p.rows > 0 && wtri > 0;
+           p.rows > 0 && wtri > 0 && slak_mlp_plan(s.M, s.C4, s.Cp, allow, &p.mlp) == SLAK_OK;
     if (s.Cp == s.C) p.ok = p.ok && (s.C % 2) == 0 && s.C <= 1024;
     else {                                                         // pitched: any parity of C; every tail op must have a kernel for (C, ldc)
         p.ok = p.ok && s.Cp > s.C && s.Cp % 8 == 0 && s.Cp <= 1024 && s.C4 == 4 * s.Cp;
         for (int op = SLAK_TAIL_LN_FWD; op <= SLAK_TAIL_SR_BWD; ++op)
             for (int sdt : {SLAK_F32, SLAK_BF16}) p.ok = p.ok && slak_block_tail_family(op, sdt, s.N, s.C, s.P, s.Cp) != SLAK_TAIL_FAMILY_NONE;
     }
-    p.nt1 = slak_linear_nt_supported(s.M, s.C4, s.Cp, 1) != 0;      // pwconv1 + GELU in one streaming pass
-    p.nt2 = slak_linear_nt_supported(s.M, s.Cp, s.C4, 0) != 0;      // pwconv2
-    p.ntd1 = slak_linear_nt_supported(s.M, s.C4, s.Cp, 0) != 0;     // dz W2
-    p.ntd2 = slak_linear_nt_supported(s.M, s.Cp, s.C4, 0) != 0;     // dy1 W1
-    p.wg1 = slak_linear_wgrad_supported(s.M, s.C4, s.Cp) != 0;      // dW1 = dy1^T t
-    p.wg2 = slak_linear_wgrad_supported(s.M, s.Cp, s.C4) != 0;      // dW2 = dz^T a
     p.bwd1 = slak_dwconv2d_tri_backward_supported(dt, s.N, s.C, s.H, s.W, s.K) == 1;
-    p.gbwd = slak_linear_nt_gelu_bwd_supported(s.M, s.C4, s.Cp) == 1;
-    p.mlp1 = slak_linear_mlp_fwd_supported(s.M, s.Cp, s.C4) == 1;
-    p.gg1 = slak_linear_gemm_supported(s.M, s.C4, s.Cp, SLAK_EPI_GELU) == 1;    // stages 2-3: pwconv1 + GELU as one GEMM launch (round 5)
-    p.gg2 = slak_linear_gemm_supported(s.M, s.C4, s.Cp, SLAK_EPI_DGELU) == 1;   //             dz W2 + GELU' + pwconv1's bias gradient
-    size_t ws = std::max(wtri, slak_bn3_workspace_bytes(s.N, s.C));
-    ws = std::max(ws, slak_block_tail_workspace_bytes(s.N, s.Cp, s.P));
-    ws = std::max(ws, slak_gelu_bwd_workspace_bytes(s.M, s.C4));
-    if (p.wg1) ws = std::max(ws, slak_linear_wgrad_workspace_bytes(s.M, s.C4, s.Cp));
-    if (p.wg2) ws = std::max(ws, slak_linear_wgrad_workspace_bytes(s.M, s.Cp, s.C4));
-    if (p.gbwd) ws = std::max(ws, slak_linear_nt_gelu_bwd_workspace_bytes(s.M, s.C4, s.Cp));
     // backward: the five calls whose final column sums are deferred into one launch keep their partial rows until then: a region each,
     // behind the scratch the other calls share -- [scale_residual][gelu'][LayerNorm][dW1][dW2]
     const auto up = [](size_t v) { return (v + 255) / 256 * 256; };
     const size_t tail = slak_block_tail_workspace_bytes(s.N, s.Cp, s.P);
-    p.len[0] = tail; p.len[2] = tail;
-    p.len[1] = std::max(slak_gelu_bwd_workspace_bytes(s.M, s.C4), p.gbwd ? slak_linear_nt_gelu_bwd_workspace_bytes(s.M, s.C4, s.Cp) : (size_t)0);
-    if (p.gg2) p.len[1] = std::max(p.len[1], slak_linear_gemm_workspace_bytes(s.M, s.C4, s.Cp, SLAK_EPI_DGELU));
-    p.len[3] = p.wg1 ? slak_linear_wgrad_workspace_bytes(s.M, s.C4, s.Cp) : 0;
-    p.len[4] = p.wg2 ? slak_linear_wgrad_workspace_bytes(s.M, s.Cp, s.C4) : 0;
-    size_t o = up(ws);
-    for (int k = 0; k < 5; ++k) { p.off[k] = o; p.len[k] = up(std::max<size_t>(p.len[k], 256)); o += p.len[k]; }
+    const size_t len[5] = {tail, p.mlp.ws_dy1, tail, p.mlp.ws_dw1, p.mlp.ws_dw2};
+    size_t o = up(std::max({wtri, slak_bn3_workspace_bytes(s.N, s.C), tail, p.mlp.ws_dy1, p.mlp.ws_dw1, p.mlp.ws_dw2}));   // (the MLP launches use their regions; leaving them out here moves the regions and made the step time bimodal: profiles/mlp_plan_step_times.jsonl)
+    for (int k = 0; k < 5; ++k) { p.off[k] = o; p.len[k] = up(std::max<size_t>(len[k], 256)); o += p.len[k]; }
     p.ws = o;
     return cache.emplace(key, p).first->second;
 }
@@ -188,14 +169,15 @@ std::vector<Tensor> block_forward(const Tensor& x, const c10::optional<Tensor>& 
                                   const Tensor& lnw, const Tensor& lnb, double ln_eps, const Tensor& w1b, const Tensor& bb1b, const Tensor& w2b,
                                   const Tensor& bb2b, const Tensor& gamma, const c10::optional<Tensor>& sample_scale, bool emit_lowp,
                                   const pybind11::object& exchange_obj /* None: single process; else see Exchange */,
-                                  int64_t ldc /* row pitch of the NHWC tensors; != C: w1b .. bb2b are the zero-padded operands */) {
+                                  int64_t ldc /* row pitch of the NHWC tensors; != C: w1b .. bb2b are the zero-padded operands */,
+                                  int64_t allow /* SLAK_MLP_ALLOW_*: block_ops' use_skinny_linear / use_linear_gemm / use_linear_wgrad */) {
     Exchange exchange(exchange_obj);
     TORCH_CHECK(w1b.dim() == 2 && w2b.dim() == 2 && ldc == w1b.size(1) && ldc == w2b.size(0) && w2b.size(1) == w1b.size(0) && bb1b.numel() == w1b.size(0) &&
                 bb2b.numel() == ldc, "the pointwise operands do not fit the pitch");
     TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 4, "x must be a contiguous (N,C,H,W) HIP tensor");
     TORCH_CHECK(bn_gamma.size() == 3 && bn_beta.size() == 3 && bn_mean.size() == 3 && bn_var.size() == 3, "three branch BatchNorms");
     const Shape s = shape_of(x, wv, w1b);
-    const Plan& pl = plan_of(s);
+    const Plan& pl = plan_of(s, (unsigned)allow);
     const bool f32w = wv.scalar_type() == at::kFloat && wh.scalar_type() == at::kFloat && wsm.scalar_type() == at::kFloat && wv.is_contiguous() &&
                       wh.is_contiguous() && wsm.is_contiguous() && wv.size(3) == 5 && wh.size(2) == 5 && wh.size(3) == s.K && wsm.size(2) == 5 && wsm.size(3) == 5;
     if (!pl.ok || !f32w || (x.scalar_type() != at::kFloat && x.scalar_type() != at::kBFloat16) || w1b.scalar_type() != at::kBFloat16) return {};
@@ -239,30 +221,31 @@ std::vector<Tensor> block_forward(const Tensor& x, const c10::optional<Tensor>& 
              "slak_ln_nchw_to_nhwc_forward_ld");
     // pwconv1 -> GELU -> pwconv2
     Tensor y1m, a, z;
-    if (pl.mlp1) {                                                 // stage 1: pwconv1, GELU and pwconv2 in one pass
-        y1m = at::empty({s.N, s.H, s.W, s.C4}, x16.options()); a = at::empty_like(y1m); z = at::empty({s.N, s.H, s.W, s.Cp}, x16.options());
+    if (pl.mlp.pw1 != SLAK_MLP_LIBRARY) { y1m = at::empty({s.N, s.H, s.W, s.C4}, x16.options()); a = at::empty_like(y1m); }
+    if (pl.mlp.pw1 == SLAK_MLP_FUSED || pl.mlp.pw2 == SLAK_MLP_NT) z = at::empty({s.N, s.H, s.W, s.Cp}, x16.options());
+    switch (pl.mlp.pw1) {
+    case SLAK_MLP_FUSED:                                           // stage 1: pwconv1, GELU and pwconv2 in one pass
         check_rc(slak_linear_mlp_fwd(t.data_ptr(), w1b.data_ptr(), bb1b.data_ptr(), w2b.data_ptr(), bb2b.data_ptr(), y1m.data_ptr(), a.data_ptr(), z.data_ptr(),
                                      s.M, s.Cp, s.C4, st), "slak_linear_mlp_fwd");
-    } else {
-    if (pl.nt1) {
-        y1m = at::empty({s.N, s.H, s.W, s.C4}, x16.options()); a = at::empty_like(y1m);
+        break;
+    case SLAK_MLP_NT:
         check_rc(slak_linear_nt(t.data_ptr(), w1b.data_ptr(), bb1b.data_ptr(), y1m.data_ptr(), a.data_ptr(), s.M, s.C4, s.Cp, st), "slak_linear_nt");
-    } else if (pl.gg1) {                                           // stages 2-3: bias, rounding and GELU in the GEMM's epilogue
-        y1m = at::empty({s.N, s.H, s.W, s.C4}, x16.options()); a = at::empty_like(y1m);
+        break;
+    case SLAK_MLP_GEMM:                                            // stages 2-3: bias, rounding and GELU in the GEMM's epilogue
         check_rc(slak_linear_gemm(t.data_ptr(), w1b.data_ptr(), bb1b.data_ptr(), y1m.data_ptr(), a.data_ptr(), nullptr, nullptr, s.M, s.C4, s.Cp, SLAK_EPI_GELU,
                                   nullptr, 0, st), "slak_linear_gemm");
-    } else {
+        break;
+    default:
         y1m = at::linear(t, w1b, bb1b);
         a = at::gelu(y1m);
     }
-    if (pl.nt2) {
-        z = at::empty({s.N, s.H, s.W, s.Cp}, x16.options());
+    if (pl.mlp.pw1 == SLAK_MLP_FUSED) {
+    } else if (pl.mlp.pw2 == SLAK_MLP_NT) {
         check_rc(slak_linear_nt(a.data_ptr(), w2b.data_ptr(), bb2b.data_ptr(), z.data_ptr(), nullptr, s.M, s.Cp, s.C4, st), "slak_linear_nt");
     } else {
         z = at::linear(a, w2b, bb2b);
         if (z.scalar_type() != at::kBFloat16) z = z.to(at::kBFloat16);
         z = z.contiguous();
-    }
     }
     // gamma * + permute + residual (+ the bf16 copy for the next block's convs)
     Tensor out = at::empty({s.N, s.C, s.H, s.W}, stats.options());
@@ -294,18 +277,16 @@ struct GradDst {
     }
 };
 
-Tensor wgrad(const Tensor& dy, const Tensor& x, int M, int N1, int N2, bool covered, const Scratch& ws, void* st, const GradDst& gd, int slot) {
+Tensor wgrad(const Tensor& dy, const Tensor& x, int M, int N1, int N2, int rung, int S, const Scratch& ws, void* st, const GradDst& gd, int slot) {
     const auto f32 = dy.options().dtype(at::kFloat);
-    if (covered) {
+    if (rung == SLAK_MLP_KERNEL) {
         Tensor d = gd.take(slot, {N1, N2}, f32);
         check_rc(slak_linear_wgrad(dy.data_ptr(), x.data_ptr(), fpm(d), M, N1, N2, ws.p, ws.n, st), "slak_linear_wgrad");
         return d;
     }
     // widths the row-reduction kernel does not cover (e.g. SLaK-B's 128 * 2^k): the reduction index M = N*H*W is split into S batches of a
     // library batched GEMM, the S partial products are added in fp32 -- what block_ops._mlp_wgrad does (a single GEMM with K = M runs on four
-    // workgroups: measured 0.86 ms per call on stage 1)
-    int S = std::max(1, M / 6272);
-    while (S > 1 && M % S) --S;
+    // workgroups: measured 0.86 ms per call on stage 1); S = slak_mlp_plan's `splits`
     if (S > 1) {
         Tensor parts = at::bmm(dy.view({S, M / S, N1}).transpose(1, 2), x.view({S, M / S, N2}));
         if (gd.usable(slot, (int64_t)N1 * N2)) {                     // the fp32 sum of the splits straight into the caller's tensor (same additions)
@@ -328,7 +309,8 @@ std::vector<Tensor> block_backward(const Tensor& x16, const Tensor& wv, const Te
                                    const c10::optional<Tensor>& count_dev, const pybind11::object& exchange_obj, const pybind11::object& trace,
                                    const c10::optional<Tensor>& w1t_opt, const c10::optional<Tensor>& w2t_opt /* cached transposed bf16 weights, or None */,
                                    const c10::optional<Tensor>& w1p_opt /* W1^T in fragment-major order (slak_linear_nt_gelu_bwd_dt), or None */,
-                                   const std::vector<c10::optional<Tensor>>& grad_dst, int64_t ldc /* as in block_forward */) {
+                                   const std::vector<c10::optional<Tensor>>& grad_dst, int64_t ldc, int64_t allow /* as in block_forward */,
+                                   bool bn_bwd_async /* block_ops._bn_bwd_async: the backward statistics exchange on the collective's own stream */) {
     Exchange exchange(exchange_obj);
     const Shape s = shape_of(x16, wv, w1b);
     TORCH_CHECK(ldc == s.Cp && z.size(-1) == ldc && t.size(-1) == ldc, "the saved tensors do not fit the pitch");
@@ -337,7 +319,7 @@ std::vector<Tensor> block_backward(const Tensor& x16, const Tensor& wv, const Te
     const GradDst gd{grad_dst.empty() ? nullptr : &grad_dst, (int)x16.get_device()};
     const GradDst gdm = pitched ? GradDst{nullptr, (int)x16.get_device()} : gd;       // dW1, db1, dW2 of a pitched block come out padded and are cut at the end
     enum { G_WV, G_WH, G_WS, G_G1, G_B1, G_G2, G_B2, G_G3, G_B3, G_LNW, G_LNB, G_W1, G_BB1, G_W2, G_BB2, G_GAMMA };
-    const Plan& pl = plan_of(s);
+    const Plan& pl = plan_of(s, (unsigned)allow);
     TORCH_CHECK(pl.ok, "block_backward: the shape has no one-launch path (block_forward would have declined it)");
     c10::hip::HIPGuard guard(x16.get_device());
     void* st = stream_of(x16);
@@ -367,33 +349,35 @@ std::vector<Tensor> block_backward(const Tensor& x16, const Tensor& wv, const Te
     const auto w2t_of = [&] { return (w2t_opt.has_value() && w2t_opt->defined()) ? *w2t_opt : w2b.t().contiguous(); };
     const auto w1t_of = [&] { return (w1t_opt.has_value() && w1t_opt->defined()) ? *w1t_opt : w1b.t().contiguous(); };
     Tensor dact, dy1, dt_, db1 = gdm.take(G_BB1, {s.C4}, f32);
-    if (pl.gbwd && w1p_opt.has_value() && w1p_opt->defined() && slak_linear_nt_gelu_bwd_dt_supported(s.M, s.C4, s.Cp) == 1) {
-        Tensor w2t = w2t_of();                                     // stage 1: the same with dt = dy1 W1 taken from the dy1 tiles while they are on chip
-        dy1 = at::empty({s.M, s.C4}, x16.options());
+    const Tensor w2t = pl.mlp.dy1 != SLAK_MLP_LIBRARY ? w2t_of() : Tensor();
+    if (pl.mlp.dy1 == SLAK_MLP_NT) dact = at::empty({s.M, s.C4}, x16.options()); else if (pl.mlp.dy1 != SLAK_MLP_LIBRARY) dy1 = at::empty({s.M, s.C4}, x16.options());
+    switch (pl.mlp.dy1) {
+    case SLAK_MLP_FUSED_DT:                                        // stage 1: FUSED with dt = dy1 W1 taken from the dy1 tiles while they are on chip
+        TORCH_CHECK(w1p_opt.has_value() && w1p_opt->defined(), "block_backward: slak_mlp_plan chose slak_linear_nt_gelu_bwd_dt, the caller gave no packed W1^T");
         dt_ = at::empty({s.M, s.Cp}, x16.options());
         check_rc(slak_linear_nt_gelu_bwd_dt(dz2.data_ptr(), w2t.data_ptr(), y1m.data_ptr(), w1p_opt->data_ptr(), dy1.data_ptr(), dt_.data_ptr(), fpm(db1), s.M, s.C4,
                                             s.Cp, region(1).p, region(1).n, st), "slak_linear_nt_gelu_bwd_dt");
-    } else if (pl.gbwd) {                                          // stage 1: dz W2, GELU' and pwconv1's bias gradient in one pass
-        Tensor w2t = w2t_of();
-        dy1 = at::empty({s.M, s.C4}, x16.options());
+        break;
+    case SLAK_MLP_FUSED:                                           // stage 1: dz W2, GELU' and pwconv1's bias gradient in one pass
         check_rc(slak_linear_nt_gelu_bwd(dz2.data_ptr(), w2t.data_ptr(), y1m.data_ptr(), dy1.data_ptr(), fpm(db1), s.M, s.C4, s.Cp, region(1).p, region(1).n, st),
                  "slak_linear_nt_gelu_bwd");
-    } else if (pl.gg2) {                                           // stages 2-3: dz W2 with GELU' and pwconv1's bias gradient in the GEMM's epilogue
-        Tensor w2t = w2t_of();
-        dy1 = at::empty({s.M, s.C4}, x16.options());
+        break;
+    case SLAK_MLP_GEMM:                                            // stages 2-3: dz W2 with GELU' and pwconv1's bias gradient in the GEMM's epilogue
         check_rc(slak_linear_gemm(dz2.data_ptr(), w2t.data_ptr(), nullptr, dy1.data_ptr(), nullptr, y1m.data_ptr(), fpm(db1), s.M, s.C4, s.Cp, SLAK_EPI_DGELU,
                                   region(1).p, region(1).n, st), "slak_linear_gemm");
-    } else {
-    if (pl.ntd1) {
-        Tensor w2t = w2t_of();
-        dact = at::empty({s.M, s.C4}, x16.options());
+        break;
+    case SLAK_MLP_NT:
         check_rc(slak_linear_nt(dz2.data_ptr(), w2t.data_ptr(), nullptr, dact.data_ptr(), nullptr, s.M, s.C4, s.Cp, st), "slak_linear_nt");
-    } else dact = at::mm(dz2, w2b);
-    dy1 = at::empty_like(dact);
-    check_rc(slak_gelu_backward_bias(dact.data_ptr(), y1m.data_ptr(), dy1.data_ptr(), fpm(db1), s.M, s.C4, region(1).p, region(1).n, st), "slak_gelu_backward_bias");
+        break;
+    default:
+        dact = at::mm(dz2, w2b);
     }
-    if (dt_.defined()) {
-    } else if (pl.ntd2) {
+    if (dact.defined()) {                                          // the NT and LIBRARY rungs: GELU' and pwconv1's bias gradient as a pass of their own
+        dy1 = at::empty_like(dact);
+        check_rc(slak_gelu_backward_bias(dact.data_ptr(), y1m.data_ptr(), dy1.data_ptr(), fpm(db1), s.M, s.C4, region(1).p, region(1).n, st), "slak_gelu_backward_bias");
+    }
+    if (pl.mlp.dy1 == SLAK_MLP_FUSED_DT) {
+    } else if (pl.mlp.dt == SLAK_MLP_NT) {
         Tensor w1t = w1t_of();
         dt_ = at::empty({s.M, s.Cp}, x16.options());
         check_rc(slak_linear_nt(dy1.data_ptr(), w1t.data_ptr(), nullptr, dt_.data_ptr(), nullptr, s.M, s.Cp, s.C4, st), "slak_linear_nt");
@@ -423,20 +407,19 @@ std::vector<Tensor> block_backward(const Tensor& x16, const Tensor& wv, const Te
         gsums = at::empty({(int64_t)s.C * 4}, f32);                 // the all-reduce's buffer: written by the same launch (no clone)
         check_rc(slak_bn3_backward_sums_dup(ds.data_ptr(), yv.data_ptr(), yh.data_ptr(), ys.data_ptr(), fp(bnstats), fpm(lsums), fpm(gsums), s.N, s.C, s.P, ws.p, ws.n, st),
                  "slak_bn3_backward_sums_dup");
-        // on the compute stream like the forward exchange (no stream hand-offs; the collective's latency is on the stream), or SLAK_BN_BWD_ASYNC=1:
-        // asynchronously (its own stream: the two weight-gradient launches below run beside it)
-        static const bool async_bwd = [] { const char* e = getenv("SLAK_BN_BWD_ASYNC"); return e && e[0] == '1'; }();      // (default since round 6: on the compute stream, block_ops._bn_bwd_async)
-        exchange.run(gsums, async_bwd);
+        // on the compute stream like the forward exchange (no stream hand-offs; the collective's latency is on the stream; the default since round 6), or
+        // bn_bwd_async: asynchronously (its own stream: the two weight-gradient launches below run beside it)
+        exchange.run(gsums, bn_bwd_async);
     }
     // the two pointwise weight gradients (single process: in front of the BatchNorm pass, as the Python node launches them)
     // (with both on the library's kernel: on the side stream, joined at the end of this function -- their operands are complete on the main
     // stream at the fork, their outputs, operands and workspace regions are not touched by the main stream before the join)
     if (!trace.is_none()) trace("pointwise_wgrads");
     Side& sd = side_of(x16.get_device());
-    const bool forked = sd.ok && pl.wg1 && pl.wg2 && hipEventRecord(sd.fork, (hipStream_t)st) == hipSuccess && hipStreamWaitEvent(sd.st, sd.fork, 0) == hipSuccess;
+    const bool forked = sd.ok && pl.mlp.dw1 == SLAK_MLP_KERNEL && pl.mlp.dw2 == SLAK_MLP_KERNEL && hipEventRecord(sd.fork, (hipStream_t)st) == hipSuccess && hipStreamWaitEvent(sd.st, sd.fork, 0) == hipSuccess;
     void* wst = forked ? (void*)sd.st : st;
-    Tensor dw1 = wgrad(dy1, t.view({s.M, s.Cp}), s.M, s.C4, s.Cp, pl.wg1, region(3), wst, gdm, G_W1);
-    Tensor dw2 = wgrad(dz2, a.view({s.M, s.C4}), s.M, s.Cp, s.C4, pl.wg2, region(4), wst, gdm, G_W2);
+    Tensor dw1 = wgrad(dy1, t.view({s.M, s.Cp}), s.M, s.C4, s.Cp, pl.mlp.dw1, pl.mlp.splits, region(3), wst, gdm, G_W1);
+    Tensor dw2 = wgrad(dz2, a.view({s.M, s.C4}), s.M, s.Cp, s.C4, pl.mlp.dw2, pl.mlp.splits, region(4), wst, gdm, G_W2);
     struct Join { Side* sd; void* st; bool on;
                   void now() { if (on && hipEventRecord(sd->join, sd->st) == hipSuccess) (void)hipStreamWaitEvent((hipStream_t)st, sd->join, 0); on = false; }
                   ~Join() { now(); } } join{&sd, st, forked};

@@ -172,3 +172,59 @@ def test_block_runner_issues_the_same_launches_as_the_python_node(gpu):
     bad = [n for n in g0 if not np.array_equal(g0[n], g1[n])] + [n for n in bg0 if not np.array_equal(bg0[n], bg1[n])]
     assert not bad, bad[:5]
     assert all(np.array_equal(r0[k], r1[k]) for k in r0)
+
+
+# (C, x shape, kernel_size, use_skinny_linear) -> the rungs of slak_mlp_plan the case is there for: (pw1, dy1, dt or None: either, dw1 = dw2, splits)
+MLP_RUNG_CASES = {
+    "c96_fused": ((2, 96, 8, 8), (13, 5), True, ("fused", "fused_dt", None, "kernel", 1)),
+    "c192_gemm": ((2, 192, 8, 8), (13, 5), True, ("gemm", "gemm", None, "kernel", 1)),
+    "c64_library": ((2, 64, 8, 8), (13, 5), True, ("library", "library", "library", "library", 1)),
+    "c64_splitk": ((4, 64, 56, 56), (51, 5), True, ("library", "library", "library", "library", 2)),
+    "c96_no_skinny": ((2, 96, 8, 8), (13, 5), False, ("library", "library", "library", "kernel", 1)),
+}
+
+
+@pytest.mark.parametrize("case", list(MLP_RUNG_CASES))
+def test_block_runner_and_python_node_follow_the_same_mlp_plan(case, gpu):
+    """Both callers of slak_mlp_plan on one block per family of rungs (the narrow model and the stage-1 block above reach the stage-1 rungs only):
+    output, x.grad and every parameter gradient bit-identical between the C++ runner and the Python sequence.  Each case first asserts that the plan
+    of its shape names the rungs it is there for, and that the runner really took the block."""
+    import ctypes
+    from slak_amd import _lib, block_ops
+    import slak_amd.slak_model as M
+    if block_ops._runner() is None:
+        pytest.skip("block runner module not built")
+    shape, ks, skinny, (pw1, dy1, dt, dw, splits) = MLP_RUNG_CASES[case]
+    C, rows = shape[1], shape[0] * shape[2] * shape[3]
+    plan = _lib.MlpPlan()
+    allow = _lib.MLP_ALLOW_ALL if skinny else _lib.MLP_ALLOW_ALL & ~_lib.MLP_ALLOW_SKINNY
+    assert _lib.lib().slak_mlp_plan(rows, 4 * C, C, allow, ctypes.byref(plan)) == 0
+    name = lambda rung: _lib.MLP_RUNG_NAMES[rung]
+    assert (name(plan.pw1), name(plan.dy1), name(plan.dw1), name(plan.dw2), plan.splits) == (pw1, dy1, dw, dw, splits)
+    assert name(plan.dt) in (("nt", "library") if dt is None else (dt,))
+    res = []
+    saved_skinny = block_ops.use_skinny_linear
+    for use in (False, True):
+        _set_fused(True, True)
+        saved = block_ops._runner_mod
+        if not use:
+            block_ops._runner_mod = None
+        block_ops.use_skinny_linear = skinny
+        try:
+            torch.manual_seed(7)
+            blk = M.Block(C, drop_path=0.0, layer_scale_init_value=0.5, kernel_size=ks, Decom=True, bn=True, lowp_dwconv=True).to(gpu)
+            blk.train()
+            x = torch.randn(*shape, device=gpu, requires_grad=True)
+            with torch.autocast("cuda", dtype=torch.bfloat16):
+                y = blk(x)
+            assert type(y.grad_fn).__name__ == "_BlockFnBackward" and y.grad_fn.runner is use     # not Python against Python
+            y.float().pow(2).mean().backward()
+            res.append((y.detach().double().cpu().numpy(), x.grad.double().cpu().numpy(), {n: p.grad.double().cpu().numpy() for n, p in blk.named_parameters()}))
+        finally:
+            block_ops.use_skinny_linear = saved_skinny
+            block_ops._runner_mod = saved
+            _set_fused(False)
+    (y0, dx0, g0), (y1, dx1, g1) = res
+    assert np.array_equal(y0, y1) and np.array_equal(dx0, dx1)
+    bad = [n for n in g0 if not np.array_equal(g0[n], g1[n])]
+    assert set(g0) == set(g1) and not bad, bad

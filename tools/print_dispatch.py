@@ -5,6 +5,7 @@
     python tools/print_dispatch.py --small            the same for the small shapes the parity tests launch -> tests/golden/dispatch_table_small.json
     python tools/print_dispatch.py --queries OUT.npz  the support / size queries (host code only, no GPU needed) over QUERY_GRID, and over the stage
                                                       shapes with each switch of QUERY_SWITCHES off -> tests/golden/dispatch_queries.npz
+    python tools/print_dispatch.py --mlp              slak_mlp_plan for the pointwise MLP of every stage of the configurations (host code only)
     python tools/print_dispatch.py --stage-queries    (what --queries runs in a child process per switch: switches are read once per process)
 
 tests/test_dispatch_gpu.py and tests/test_dispatch_queries.py load table(), small_shapes(), queries() from this file by path."""
@@ -136,8 +137,22 @@ def all_queries():
     return out
 
 
+def mlp_plans():
+    """{stage: {step: rung}}: slak_mlp_plan (allow = every kernel family) for the pointwise MLP of every stage of CONFIGS.  Host code only."""
+    lib = _load("slak_amd/_lib.py", "_slak_lib_only")
+    L, out = lib.lib(), {}
+    for cfg, (N, stages) in CONFIGS.items():
+        for si, (C, HW, _) in enumerate(stages):
+            p = lib.MlpPlan()
+            lib.check(L.slak_mlp_plan(N * HW * HW, 4 * C, C, lib.MLP_ALLOW_ALL, ctypes.byref(p)), "slak_mlp_plan")
+            out["%s/s%d" % (cfg, si + 1)] = dict({f: lib.MLP_RUNG_NAMES[getattr(p, f)] for f in ("pw1", "pw2", "dy1", "dt", "dw1", "dw2")}, splits=p.splits)
+    return out
+
+
 if __name__ == "__main__":
-    if "--stage-queries" in sys.argv:
+    if "--mlp" in sys.argv:
+        print(json.dumps(mlp_plans(), indent=0))
+    elif "--stage-queries" in sys.argv:
         print(json.dumps(queries(load_lib(), STAGE_POINTS)))
     elif "--queries" in sys.argv:
         import numpy as np
