@@ -552,6 +552,36 @@ int slak_adamw_plan_create(const slak_adamw_segment_t* segs_host, int nseg, slak
 int slak_adamw_step(slak_adamw_plan_t* plan, const void* const* grads_dev, const slak_adamw_group_t* groups_host, int ngroups, void* stream);
 int slak_adamw_plan_destroy(slak_adamw_plan_t* plan);
 
+/* Gradient norm, clipping and loss-scale handling folded around slak_adamw_step: what NativeScalerWithGradNormCount.__call__
+ * (utils.py:384-404) does between backward() and the optimizer step, over the SAME plan and the same device table of gradient pointers.
+ * Vector loads and stores only, no atomics, every reduction in a fixed order: bitwise reproducible.  No entry synchronises the host.
+ *
+ * A zero-element tensor has no chunk; slak_adamw_plan_create accepts NULL param / exp_avg / exp_avg_sq pointers for it (torch gives it no storage).
+ *
+ * slak_adamw_plan_blocks: the number of 4096-element chunks of the plan = the number of partials slak_grad_sumsq writes for it
+ * (a count, so an invalid plan is reported as -SLAK_ERR_INVALID_ARG, which no count can be).
+ *
+ * slak_grad_sumsq = the read half of GradScaler.unscale_ (torch/amp/grad_scaler.py, _unscale_grads_ ->
+ * _amp_foreach_non_finite_check_and_unscale_) and the per-parameter torch.norm(p.grad, 2) of get_grad_norm_ (utils.py:424) /
+ * clip_grad_norm_ (utils.py:396): partials_dev[offset + b] = sum over chunk b of ((double)u)^2, u = g * *inv_scale_dev rounded to fp32 once
+ * (inv_scale_dev NULL: 1).  A chunk holding an inf or NaN gradient writes a non-finite partial; a NULL gradient pointer writes 0.
+ * The gradients are only read.  One launch per plan; a model with more than SLAK_ADAMW_MAX_GROUPS groups has several plans that write
+ * disjoint ranges of one partials array.
+ *
+ * slak_grad_norm_finish = the outer torch.norm(torch.stack(...)) of utils.py:424, clip_grad_norm_'s clip_coef (utils.py:396) and the
+ * found_inf test of GradScaler.step (utils.py:400), WITHOUT its .item(): one workgroup sums the n partials (n = 0: norm 0) in fp64 and
+ * writes ctl_dev[4] = { inv_scale, clip_coef = min(1, max_norm / (norm + 1e-6)) or 1 when max_norm < 0, found_inf (0 or 1),
+ * norm = (float)sqrt(total), inf or NaN on overflow }.
+ *
+ * slak_adamw_step_scaled = GradScaler.step(optimizer) (utils.py:400) with the write halves of unscale_ and clip_grad_norm_: slak_adamw_step
+ * on g' = (g * ctl[0]) * ctl[1] (two separately rounded products), and no write at all when ctl[2] is set.  The gradients are not modified.
+ * The step counts must have been advanced by the caller only when ctl[2] is 0 (a device-side op; slak_amd.optim_factory does it). */
+int slak_adamw_plan_blocks(const slak_adamw_plan_t* plan);
+int slak_grad_sumsq(slak_adamw_plan_t* plan, const void* const* grads_dev, const float* inv_scale_dev, double* partials_dev, long long offset, void* stream);
+int slak_grad_norm_finish(const double* partials_dev, int n, const float* inv_scale_dev, double max_norm /* < 0: no clipping */, float* ctl_dev, void* stream);
+int slak_adamw_step_scaled(slak_adamw_plan_t* plan, const void* const* grads_dev, const slak_adamw_group_t* groups_host, int ngroups, const float* ctl_dev,
+                           void* stream);
+
 /* slak_ema_update = ModelEma.update(model, mask) (model_sema.py:67-91) over every state-dict entry:
  *   dense  : ema = ema*decay + (1-decay)*model
  *   masked : ema = (ema*decay + model*(1-decay))*mask + (diff*decay)*model,  diff = ((ema != 0) ^ mask) & mask  (newly grown weights)

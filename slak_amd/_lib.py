@@ -84,6 +84,10 @@ SIGNATURES = {
     "slak_adamw_plan_create": (_i, [ctypes.POINTER(AdamwSegment), _i, ctypes.POINTER(_vp)]),
     "slak_adamw_step": (_i, [_vp, _vp, ctypes.POINTER(AdamwGroup), _i, _vp]),
     "slak_adamw_plan_destroy": (_i, [_vp]),
+    "slak_adamw_plan_blocks": (_i, [_vp]),                        # chunks of the plan (= partials of slak_grad_sumsq), or -ERR_INVALID_ARG
+    "slak_grad_sumsq": (_i, [_vp, _vp, _vp, _vp, ctypes.c_longlong, _vp]),      # (plan, grads table, inv_scale | NULL, fp64 partials, offset, stream)
+    "slak_grad_norm_finish": (_i, [_vp, _i, _vp, _d, _vp, _vp]),  # (partials, n, inv_scale | NULL, max_norm (< 0: none), ctl[4], stream)
+    "slak_adamw_step_scaled": (_i, [_vp, _vp, ctypes.POINTER(AdamwGroup), _i, _vp, _vp]),
     "slak_ema_plan_create": (_i, [ctypes.POINTER(EmaSegment), _i, ctypes.POINTER(_vp)]),
     "slak_ema_update": (_i, [_vp, _d, _vp]),
     "slak_ema_plan_destroy": (_i, [_vp]),

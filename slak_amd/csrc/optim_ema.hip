@@ -5,6 +5,10 @@
 //                     kernels, then one elementwise multiply per masked tensor from a Python loop (~100 launches for SLaK-T).
 //   slak_ema_update : ModelEma.update(model, mask) (model_sema.py:67-91) as ONE launch over all state-dict entries.  The
 //                     reference loops over ~600 entries in Python with 4 (dense) to 11 (masked) elementwise kernels each.
+//   slak_grad_sumsq / slak_grad_norm_finish / slak_adamw_step_scaled: what NativeScalerWithGradNormCount.__call__
+//                     (utils.py:384-404) does to the gradients between backward() and the step -- GradScaler.unscale_, get_grad_norm_
+//                     (utils.py:413-425; one torch.norm per parameter) or clip_grad_norm_, the found_inf test -- as one read pass over
+//                     the gradients, one single-workgroup reduction, and the AdamW launch reading a four-float device record.
 //
 // Both are pure streaming passes (HBM-bound: 28 B/element for AdamW without mask, 12-16 B/element for the EMA); a workgroup owns one
 // 4096-element chunk of one tensor (table lookup by blockIdx), 16-byte accesses when every pointer of the tensor is 16-byte
@@ -38,9 +42,24 @@ __device__ __forceinline__ float adamw_elem(float p, float g, float& m, float& v
     return p + k.neg_step_size * (m / denom);    // param.addcdiv_(exp_avg, denom, value=-step_size)
 }
 
+// the gradient the update sees.  SCALED: (g * inv_scale) * clip_coef, two separately rounded products -- what GradScaler.unscale_
+// (_amp_foreach_non_finite_check_and_unscale_) followed by clip_grad_norm_'s g.mul_(clip_coef) leave in the gradient tensor
+template <bool SCALED> __device__ __forceinline__ float adamw_grad(float g, float inv_scale, float clip_coef) {
+    if constexpr (SCALED) return (g * inv_scale) * clip_coef;
+    else return g;
+}
+
+// SCALED = false is slak_adamw_step (ctl unused).  SCALED = true reads the control record slak_grad_norm_finish wrote:
+// ctl[0] inv_scale, ctl[1] clip_coef, ctl[2] found_inf -- a step with a non-finite gradient writes NOTHING (GradScaler.step skips it)
+template <bool SCALED>
 __global__ __launch_bounds__(OE_THREADS) void adamw_kernel(const slak_adamw_segment_t* __restrict__ segs, const int* __restrict__ blk_seg,
                                                            const int* __restrict__ seg_blk0, const float* const* __restrict__ grads,
-                                                           const AdamwGroups G) {
+                                                           const AdamwGroups G, const float* __restrict__ ctl) {
+    float inv_scale = 1.0f, clip_coef = 1.0f;
+    if constexpr (SCALED) {
+        if (ctl[2] != 0.0f) return;
+        inv_scale = ctl[0]; clip_coef = ctl[1];
+    }
     const int s = blk_seg[blockIdx.x];
     const slak_adamw_segment_t sg = segs[s];
     const float* __restrict__ g = grads[s];
@@ -70,7 +89,9 @@ __global__ __launch_bounds__(OE_THREADS) void adamw_kernel(const slak_adamw_segm
         for (int it = 0; it < OE_ITERS; ++it) {
             const long long i = base + (long long)(it * OE_THREADS + threadIdx.x) * OE_VEC;
             float4 p = *(const float4*)(P + i), m = *(const float4*)(M + i), v = *(const float4*)(V + i);
-            const float4 gr = *(const float4*)(g + i);
+            float4 gr = *(const float4*)(g + i);
+            gr.x = adamw_grad<SCALED>(gr.x, inv_scale, clip_coef); gr.y = adamw_grad<SCALED>(gr.y, inv_scale, clip_coef);
+            gr.z = adamw_grad<SCALED>(gr.z, inv_scale, clip_coef); gr.w = adamw_grad<SCALED>(gr.w, inv_scale, clip_coef);
             p.x = adamw_elem(p.x, gr.x, m.x, v.x, k); p.y = adamw_elem(p.y, gr.y, m.y, v.y, k);
             p.z = adamw_elem(p.z, gr.z, m.z, v.z, k); p.w = adamw_elem(p.w, gr.w, m.w, v.w, k);
             if (K) { const float4 mk = *(const float4*)(K + i); p.x = p.x * mk.x; p.y = p.y * mk.y; p.z = p.z * mk.z; p.w = p.w * mk.w; }
@@ -87,12 +108,85 @@ __global__ __launch_bounds__(OE_THREADS) void adamw_kernel(const slak_adamw_segm
             const long long i = base + j * OE_THREADS + threadIdx.x;
             if (i < sg.numel) {
                 float m = M[i], v = V[i];
-                float p = adamw_elem(P[i], g[i], m, v, k);
+                float p = adamw_elem(P[i], adamw_grad<SCALED>(g[i], inv_scale, clip_coef), m, v, k);
                 if (K) p = p * K[i];
                 P[i] = p; M[i] = m; V[i] = v;
                 if (B) B[i] = f32_to_bf16_bits(p);
             }
         }
+    }
+}
+
+// ---- gradient norm -----------------------------------------------------------------------------------------------------
+// fixed-order sum of one fp64 value per thread: a shuffle tree inside each wave, then the four wave sums in wave order.  Thread 0 holds
+// the result.  No atomics anywhere: the same inputs give the same bits on every run.
+__device__ __forceinline__ double block_sum_f64(double v, double* sh /*[OE_THREADS / 64]*/) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = v + __shfl_down(v, off, 64);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double t = sh[0];
+#pragma unroll
+    for (int w = 1; w < OE_THREADS / 64; ++w) t = t + sh[w];
+    return t;
+}
+
+// u = g * inv_scale rounded to fp32 once (what unscale_ leaves in the tensor), then u * u exactly and the running sum in fp64
+__device__ __forceinline__ double sumsq_elem(float g, float inv_scale) { const float u = g * inv_scale; return (double)u * (double)u; }
+
+// One fp64 partial per 4096-element chunk: partials[blockIdx.x] = sum over the chunk of (g * inv_scale)^2.  An inf or NaN gradient gives
+// an inf or NaN square, and a sum that meets one stays non-finite (squares are never negative, so no inf - inf): a non-finite partial says
+// exactly that the chunk held a non-finite gradient (squares of finite fp32 values cannot overflow fp64).  NULL gradient: partial 0.
+__global__ __launch_bounds__(OE_THREADS) void grad_sumsq_kernel(const slak_adamw_segment_t* __restrict__ segs, const int* __restrict__ blk_seg,
+                                                                const int* __restrict__ seg_blk0, const float* const* __restrict__ grads,
+                                                                const float* __restrict__ inv_scale_dev, double* __restrict__ partials) {
+    __shared__ double sh[OE_THREADS / 64];
+    const int s = blk_seg[blockIdx.x];
+    const float* __restrict__ g = grads[s];
+    if (!g) { if (threadIdx.x == 0) partials[blockIdx.x] = 0.0; return; }
+    const long long numel = segs[s].numel;
+    const float inv_scale = inv_scale_dev ? *inv_scale_dev : 1.0f;
+    const long long base = (long long)(blockIdx.x - seg_blk0[s]) * OE_BLOCK_ELEMS;
+    double acc = 0.0;
+    if (((uintptr_t)g & 15) == 0 && base + OE_BLOCK_ELEMS <= numel) {
+#pragma unroll
+        for (int it = 0; it < OE_ITERS; ++it) {
+            const long long i = base + (long long)(it * OE_THREADS + threadIdx.x) * OE_VEC;
+            const float4 gr = *(const float4*)(g + i);
+            acc = acc + sumsq_elem(gr.x, inv_scale); acc = acc + sumsq_elem(gr.y, inv_scale);
+            acc = acc + sumsq_elem(gr.z, inv_scale); acc = acc + sumsq_elem(gr.w, inv_scale);
+        }
+    } else {
+        for (int j = 0; j < OE_VEC * OE_ITERS; ++j) {
+            const long long i = base + j * OE_THREADS + threadIdx.x;
+            if (i < numel) acc = acc + sumsq_elem(g[i], inv_scale);
+        }
+    }
+    const double t = block_sum_f64(acc, sh);
+    if (threadIdx.x == 0) partials[blockIdx.x] = t;
+}
+
+// ONE workgroup: thread t adds partials[t], partials[t + 256], ... in that order, then the fixed-order block sum.
+// ctl = { inv_scale, clip_coef, found_inf, norm }.  clip_coef = min(1, max_norm / (norm + 1e-6)) (torch.nn.utils.clip_grad_norm_),
+// evaluated in fp64 from the fp32 norm and rounded once; 1 when max_norm < 0 (no clipping) -- and 1 on overflow, where nothing is applied.
+__global__ __launch_bounds__(OE_THREADS) void grad_norm_finish_kernel(const double* __restrict__ partials, int n, const float* __restrict__ inv_scale_dev,
+                                                                      double max_norm, float* __restrict__ ctl) {
+    __shared__ double sh[OE_THREADS / 64];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n; i += OE_THREADS) acc = acc + partials[i];
+    const double total = block_sum_f64(acc, sh);
+    if (threadIdx.x == 0) {
+        const float norm = (float)sqrt(total);                            // inf / NaN on overflow, as timm logs it
+        const bool bad = !(total - total == 0.0);                         // inf - inf and NaN - NaN are NaN
+        float coef = 1.0f;
+        if (max_norm >= 0.0 && !bad) {
+            const double q = max_norm / ((double)norm + 1e-6);
+            coef = q < 1.0 ? (float)q : 1.0f;
+        }
+        ctl[0] = inv_scale_dev ? *inv_scale_dev : 1.0f;
+        ctl[1] = coef;
+        ctl[2] = bad ? 1.0f : 0.0f;
+        ctl[3] = norm;
     }
 }
 
@@ -185,7 +279,8 @@ int slak_adamw_plan_create(const slak_adamw_segment_t* segs_host, int nseg, slak
     std::vector<long long> numel(nseg);
     for (int s = 0; s < nseg; ++s) {
         const slak_adamw_segment_t& g = segs_host[s];
-        if (!g.param || !g.exp_avg || !g.exp_avg_sq || !g.step || g.numel < 0 || g.group < 0 || g.group >= SLAK_ADAMW_MAX_GROUPS)
+        // a zero-element tensor has no storage (NULL pointers) and no chunk: no kernel ever sees its entry
+        if (g.numel < 0 || (g.numel > 0 && (!g.param || !g.exp_avg || !g.exp_avg_sq)) || !g.step || g.group < 0 || g.group >= SLAK_ADAMW_MAX_GROUPS)
             return SLAK_ERR_INVALID_ARG;
         numel[s] = g.numel;
     }
@@ -206,8 +301,38 @@ int slak_adamw_step(slak_adamw_plan_t* p, const void* const* grads_dev, const sl
     if (p->tab.nblk == 0) return SLAK_OK;
     AdamwGroups G;
     for (int i = 0; i < SLAK_ADAMW_MAX_GROUPS; ++i) G.g[i] = groups_host[i < ngroups ? i : 0];
-    hipLaunchKernelGGL(adamw_kernel, dim3(p->tab.nblk), dim3(OE_THREADS), 0, (hipStream_t)stream, p->segs, p->tab.blk_seg, p->tab.seg_blk0,
-                       (const float* const*)grads_dev, G);
+    hipLaunchKernelGGL(adamw_kernel<false>, dim3(p->tab.nblk), dim3(OE_THREADS), 0, (hipStream_t)stream, p->segs, p->tab.blk_seg, p->tab.seg_blk0,
+                       (const float* const*)grads_dev, G, (const float*)nullptr);
+    SLAK_LAUNCH_CHECK();
+    return SLAK_OK;
+}
+
+int slak_adamw_step_scaled(slak_adamw_plan_t* p, const void* const* grads_dev, const slak_adamw_group_t* groups_host, int ngroups, const float* ctl_dev,
+                           void* stream) {
+    if (!p || !grads_dev || !groups_host || ngroups <= 0 || ngroups > SLAK_ADAMW_MAX_GROUPS || !ctl_dev) return SLAK_ERR_INVALID_ARG;
+    if (p->tab.nblk == 0) return SLAK_OK;
+    AdamwGroups G;
+    for (int i = 0; i < SLAK_ADAMW_MAX_GROUPS; ++i) G.g[i] = groups_host[i < ngroups ? i : 0];
+    hipLaunchKernelGGL(adamw_kernel<true>, dim3(p->tab.nblk), dim3(OE_THREADS), 0, (hipStream_t)stream, p->segs, p->tab.blk_seg, p->tab.seg_blk0,
+                       (const float* const*)grads_dev, G, ctl_dev);
+    SLAK_LAUNCH_CHECK();
+    return SLAK_OK;
+}
+
+int slak_adamw_plan_blocks(const slak_adamw_plan_t* p) { return p ? p->tab.nblk : -SLAK_ERR_INVALID_ARG; }
+
+int slak_grad_sumsq(slak_adamw_plan_t* p, const void* const* grads_dev, const float* inv_scale_dev, double* partials_dev, long long offset, void* stream) {
+    if (!p || !grads_dev || !partials_dev || offset < 0) return SLAK_ERR_INVALID_ARG;
+    if (p->tab.nblk == 0) return SLAK_OK;
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(p->tab.nblk), dim3(OE_THREADS), 0, (hipStream_t)stream, p->segs, p->tab.blk_seg, p->tab.seg_blk0,
+                       (const float* const*)grads_dev, inv_scale_dev, partials_dev + offset);
+    SLAK_LAUNCH_CHECK();
+    return SLAK_OK;
+}
+
+int slak_grad_norm_finish(const double* partials_dev, int n, const float* inv_scale_dev, double max_norm, float* ctl_dev, void* stream) {
+    if (n < 0 || (n > 0 && !partials_dev) || !ctl_dev || max_norm != max_norm) return SLAK_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(OE_THREADS), 0, (hipStream_t)stream, partials_dev, n, inv_scale_dev, max_norm, ctl_dev);
     SLAK_LAUNCH_CHECK();
     return SLAK_OK;
 }

@@ -101,6 +101,8 @@ class MaskedAdamW(optim.Optimizer):
         self._grad_key = None
         self._grad_tabs = None
         self._active = None         # per-parameter 0/1 step increments when some gradients are missing (None: all present)
+        self._norm_blocks = None    # step_with_grad_norm: (plans they belong to, chunks per plan, fp64 partials)
+        self.last_grad_control = None   # step_with_grad_norm: device record [inv_scale, clip_coef, found_inf, norm] of the latest call
 
     # -- Masking hook ---------------------------------------------------------------------------------------------
     def set_masks(self, masks):
@@ -214,9 +216,32 @@ class MaskedAdamW(optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        self._step(False, None, None)
+        return loss
+
+    @torch.no_grad()
+    def step_with_grad_norm(self, clip_grad=None, inv_scale=None):
+        """The step with what utils.NativeScalerWithGradNormCount.__call__ (utils.py:384-404) does to the gradients first, on
+        ``2 * plans + 1`` launches and no host synchronisation: the 2-norm over all gradients of ``g * inv_scale``
+        (GradScaler.unscale_, then get_grad_norm_ / clip_grad_norm_), the clip coefficient ``min(1, clip_grad / (norm + 1e-6))``,
+        and an update that sees ``(g * inv_scale) * clip_coef`` -- or no update at all, step counts included, when a gradient is
+        inf or NaN (GradScaler.step).  The gradient tensors themselves are only read.
+
+        ``clip_grad``: Python float or None (no clipping).  ``inv_scale``: 0-dim fp32 tensor on the parameters' device, or None (1).
+        Returns the norm as a 0-dim fp32 device tensor (inf or NaN on overflow); ``last_grad_control`` keeps the device record
+        ``[inv_scale, clip_coef, found_inf, norm]`` of the latest call."""
+        if clip_grad is not None:
+            clip_grad = float(clip_grad)
+            if not clip_grad >= 0.0:
+                raise ValueError("clip_grad must be a non-negative number or None")
+        if inv_scale is not None and not (torch.is_tensor(inv_scale) and inv_scale.dtype == torch.float32 and inv_scale.numel() == 1 and inv_scale.is_cuda):
+            raise _lib.SlakHipError("inv_scale must be a one-element float32 tensor on the parameters' device, or None")
+        return self._step(True, clip_grad, inv_scale)
+
+    def _step(self, scaled, clip_grad, inv_scale):
         params = self._all_params()
         if not params:
-            return loss
+            return torch.zeros(()) if scaled else None          # get_grad_norm_ of no parameters (utils.py:418-419)
         for g in self.param_groups:
             if g.get("amsgrad") or g.get("maximize") or g.get("decoupled_weight_decay") is False:
                 raise NotImplementedError("MaskedAdamW implements AdamW (decoupled weight decay) without amsgrad / maximize")
@@ -239,12 +264,19 @@ class MaskedAdamW(optim.Optimizer):
                 at += len(ps)
             self._grad_tabs, self._grad_key = tabs, gkey
             self._active = None if all(gkey) else torch.tensor([1.0 if k else 0.0 for k in gkey], device=dev)
-        if self._active is None:
+        L = _lib.lib()
+        stream = _stream(dev)
+        if scaled:
+            ctl = self._grad_norm_pass(L, dev, stream, clip_grad, inv_scale)
+            live = 1.0 - ctl[2]                                   # 0 on overflow: a skipped step does not advance the bias corrections
+            if self._active is None:
+                self._steps.add_(live)
+            else:
+                self._steps.addcmul_(self._active, live)
+        elif self._active is None:
             self._steps.add_(1.0)
         else:
             self._steps.add_(self._active)
-        L = _lib.lib()
-        stream = _stream(dev)
         with _on(dev):
             for (h, ps, g0, ng, cached), tab in zip(self._plans, self._grad_tabs):
                 hyp = (_lib.AdamwGroup * ng)()
@@ -252,7 +284,10 @@ class MaskedAdamW(optim.Optimizer):
                     g = self.param_groups[g0 + k]
                     hyp[k].lr, hyp[k].beta1, hyp[k].beta2 = float(g["lr"]), float(g["betas"][0]), float(g["betas"][1])
                     hyp[k].eps, hyp[k].weight_decay = float(g["eps"]), float(g["weight_decay"])
-                _lib.check(L.slak_adamw_step(h, tab.data_ptr(), hyp, ng, stream), "slak_adamw_step")
+                if scaled:
+                    _lib.check(L.slak_adamw_step_scaled(h, tab.data_ptr(), hyp, ng, ctl.data_ptr(), stream), "slak_adamw_step_scaled")
+                else:
+                    _lib.check(L.slak_adamw_step(h, tab.data_ptr(), hyp, ng, stream), "slak_adamw_step")
         # the kernel wrote through raw pointers: bump the autograd version counters, and mark the bf16 copies it refreshed as current
         from .sparse_core import Masking
         Masking._bump_versions([p for (_, p), k in zip(params, gkey) if k])
@@ -260,7 +295,32 @@ class MaskedAdamW(optim.Optimizer):
             for p, e in cached:
                 if p.grad is not None:
                     e[1] = p._version
-        return loss
+        return ctl[3].clone() if scaled else None               # a copy: the record is overwritten by the next call
+
+    def _grad_norm_pass(self, L, dev, stream, clip_grad, inv_scale):
+        """slak_grad_sumsq once per plan into one fp64 array, slak_grad_norm_finish once over all of it; returns the control record."""
+        if inv_scale is not None and inv_scale.device != dev:
+            raise _lib.SlakHipError("inv_scale must be on the parameters' device")
+        blocks = self._norm_blocks
+        if blocks is None or blocks[0] is not self._plans:
+            counts = [L.slak_adamw_plan_blocks(h) for h, *_ in self._plans]
+            if min(counts) < 0:
+                raise _lib.SlakHipError("slak_adamw_plan_blocks failed")
+            # one fp64 partial per chunk, over all plans (the norm is over every group)
+            self._norm_blocks = blocks = (self._plans, counts, torch.empty(max(1, sum(counts)), dtype=torch.float64, device=dev))
+        if self.last_grad_control is None or self.last_grad_control.device != dev:
+            self.last_grad_control = torch.zeros(4, dtype=torch.float32, device=dev)
+        _, counts, partials = blocks
+        ctl = self.last_grad_control
+        scale_ptr = inv_scale.data_ptr() if inv_scale is not None else None
+        with _on(dev):
+            at = 0
+            for (h, *_), tab, n in zip(self._plans, self._grad_tabs, counts):
+                _lib.check(L.slak_grad_sumsq(h, tab.data_ptr(), scale_ptr, partials.data_ptr(), at, stream), "slak_grad_sumsq")
+                at += n
+            _lib.check(L.slak_grad_norm_finish(partials.data_ptr(), at, scale_ptr, -1.0 if clip_grad is None else clip_grad, ctl.data_ptr(), stream),
+                       "slak_grad_norm_finish")
+        return ctl
 
 
 # ------------------------------------------------------------------------------------------------------------------ factory

@@ -350,8 +350,18 @@ class Masking(object):
             self._opt_masks_key = key
         return True
 
-    def step(self):
-        if self._bind_optimizer_masks():
+    def step(self, clip_grad=None):
+        """sparse_core.py:300-314.  ``clip_grad`` (not in the reference, whose bf16 path has no clipping: engine.py:78-88): take the
+        step through MaskedAdamW.step_with_grad_norm and return the gradient 2-norm as a 0-dim device tensor.  truncate_weights
+        below still sees the unclipped gradients; gradient growth ranks |g| within a tensor, which a global factor does not reorder."""
+        norm = None
+        if clip_grad is not None:
+            if not (self._bind_optimizer_masks() and hasattr(self.optimizer, "step_with_grad_norm")):
+                raise _lib.SlakHipError("Masking.step(clip_grad=...) needs a slak_amd.optim_factory.MaskedAdamW; there is no fallback")
+            if self.args.distributed:
+                self.synchronism_masks()
+            norm = self.optimizer.step_with_grad_norm(clip_grad=clip_grad)
+        elif self._bind_optimizer_masks():
             if self.args.distributed:
                 self.synchronism_masks()
             self.optimizer.step()                       # AdamW update and w *= mask in one launch (sparse_core.py:300-303)
@@ -366,6 +376,7 @@ class Masking(object):
                 print('*********************************Dynamic Sparsity********************************')
                 self.truncate_weights()
                 self.print_nonzero_counts()
+        return norm
 
     def apply_mask(self):
         if self.args.distributed:

@@ -13,6 +13,9 @@ SLAK_PAD_EVEN=1 also pads the even widths 124 / 998 (block_ops.pad_even_widths).
 torch's nn.CrossEntropyLoss(label_smoothing=0.1); head_hits_per_step / fused_hits_per_step count the calls the two kernels served.
 --mixup (with --criterion soft_target) runs slak_amd.mixup.Mixup with the recipes' setting (mixup 0.8, cutmix 1.0, smoothing 0.1, 'batch' mode) on the
 batch and the hard labels in every step, as engine.py:49-50 does, and adds "mixup" / "mixup_hits_per_step" to the line; without the flag nothing changes.
+--clip-grad V takes the step through MaskedAdamW.step_with_grad_norm(clip_grad=V) (gradient norm, clipping and the step on 2 * plans + 1 launches:
+DESIGN 11); --scaler drives backward and the step through slak_amd.scaler.NativeScalerWithGradNormCount(enabled=False) (bf16 needs no loss scaling),
+with --clip-grad's value if given.  Either adds "clip_grad" / "scaler" / "grad_norm" to the line; without them the step is opt.step() as before.
 """
 import argparse
 import json
@@ -41,6 +44,8 @@ def main():
     ap.add_argument("--criterion", choices=("label_smoothing", "soft_target"), default=None,
                     help="the criterion of slak_amd.loss on its HIP kernel (default: torch's nn.CrossEntropyLoss(label_smoothing=0.1))")
     ap.add_argument("--mixup", action="store_true", help="slak_amd.mixup.Mixup on every batch (needs --criterion soft_target)")
+    ap.add_argument("--clip-grad", type=float, default=None, help="step through MaskedAdamW.step_with_grad_norm(clip_grad=V)")
+    ap.add_argument("--scaler", action="store_true", help="backward + step through slak_amd.scaler.NativeScalerWithGradNormCount(enabled=False)")
     a = ap.parse_args()
     if a.mixup and a.criterion != "soft_target":
         ap.error("--mixup needs --criterion soft_target (main.py:397-399)")
@@ -92,12 +97,24 @@ def main():
         np.random.seed(0)
         mixup_fn = slak_mixup.Mixup(mixup_alpha=0.8, cutmix_alpha=1.0, label_smoothing=0.1, num_classes=1000)
 
+    loss_scaler = None
+    if a.scaler:
+        from slak_amd.scaler import NativeScalerWithGradNormCount
+        loss_scaler = NativeScalerWithGradNormCount(enabled=False)
+    grad_norm = [None]
+
     def step():
         x, t = (samples, targets) if mixup_fn is None else mixup_fn(samples, hard)
         with torch.autocast("cuda", dtype=torch.bfloat16):
             loss = criterion(model(x), t)
-        loss.backward()
-        opt.step()
+        if loss_scaler is not None:
+            grad_norm[0] = loss_scaler(loss, opt, clip_grad=a.clip_grad, parameters=model.parameters())
+        else:
+            loss.backward()
+            if a.clip_grad is not None:
+                grad_norm[0] = opt.step_with_grad_norm(clip_grad=a.clip_grad)
+            else:
+                opt.step()
         opt.zero_grad(set_to_none=True)
         return loss
 
@@ -118,6 +135,8 @@ def main():
     rhits = getattr(block_ops, "pitched_runner_hits", 0) - rhits0
     head_hits, fused_hits = block_ops.head_hits - head0, slak_loss.fused_hits - fused0
     extra = {"mixup": True, "mixup_hits_per_step": (slak_mixup.fused_hits - mix0) / max(1, a.steps)} if a.mixup else {}
+    if grad_norm[0] is not None:
+        extra.update({"clip_grad": a.clip_grad, "scaler": bool(a.scaler), "grad_norm": float(grad_norm[0])})
     host = float("inf")
     for _ in range(3):
         h0 = time.perf_counter()
