@@ -319,6 +319,7 @@ int slak_dwconv2d_tri_forward_stats(const void* x, const float* w_v, const float
 /* The three weight gradients of a block's branches in one launch: which kernel, decided here and nowhere else */
 enum TriWgradKernel { TRI_WGRAD_NONE, TRI_WGRAD_SMALL, TRI_WGRAD_ROWS, TRI_WGRAD_WAVE };
 static TriWgradKernel tri_wgrad_kernel(int dtype, int N, int C, int H, int W, int K) {
+    if (wgrad_reduce_forced()) return TRI_WGRAD_NONE;                                             // the one-launch kernels finish through the arrival counters only
     if (dwconv_mfma_small_tri_wgrad_supported(N, C, H, W, K, dtype)) return TRI_WGRAD_SMALL;
     if (dwconv_mfma_tri_wgrad_rows_supported(N, C, H, W, K, dtype)) return TRI_WGRAD_ROWS;        // planes of 2 x 2 tiles (56 x 56 class)
     if (dwconv_mfma_tri_wgrad_wave_supported(N, C, H, W, K, dtype)) return TRI_WGRAD_WAVE;        // planes of one tile (28 x 28 class)
@@ -350,7 +351,7 @@ int slak_dwconv2d_tri_backward_filter(const void* dy_v, const void* dy_h, const 
 /* Data gradient AND the three weight gradients of a block's branches in ONE launch (the 14 x 14 class: the dY planes are staged once for
  * both).  Same bits as slak_dwconv2d_tri_backward_data + slak_dwconv2d_tri_backward_filter; workspace: slak_dwconv2d_tri_filter_workspace_bytes. */
 int slak_dwconv2d_tri_backward_supported(int dtype, int N, int C, int H, int W, int K) {
-    return dwconv_mfma_small_tri_bwd_supported(N, C, H, W, K, dtype) ? 1 : 0;
+    return (!wgrad_reduce_forced() && dwconv_mfma_small_tri_bwd_supported(N, C, H, W, K, dtype)) ? 1 : 0;
 }
 
 int slak_dwconv2d_tri_backward(const void* dy_v, const void* dy_h, const void* dy_s, const void* x, const float* w_v, const float* w_h,
@@ -363,9 +364,11 @@ int slak_dwconv2d_tri_backward(const void* dy_v, const void* dy_h, const void* d
 
 /* The K x 5 and the 5 x 5 weight gradient of a block in ONE launch where the three-branch launch above does not reach (x and its five
  * column-shifted operands are shared: the 5 x 5 correlation is the K x 5 one with its own dY).  0 / SLAK_ERR_UNSUPPORTED: two calls.
- * Which kernel is decided here and nowhere else; the launch also honours the algo switch and SLAK_MFMA_DMA, the size query does not. */
+ * Which kernel is decided here and nowhere else; the launch also honours the algo switch (slak_set_conv_algo can change between the query and
+ * the launch), the size query does not. */
 enum PairWgradKernel { PAIR_WGRAD_NONE, PAIR_WGRAD_VWAVE, PAIR_WGRAD_VROWS };
 static PairWgradKernel pair_wgrad_kernel(const ConvDims& d, int dtype) {
+    if (!use_dma() || wgrad_reduce_forced()) return PAIR_WGRAD_NONE;                              // (read once per process: a cached answer stays true)
     if (dwconv_mfma_wgrad_vwave_supported(d, dtype, dtype)) return PAIR_WGRAD_VWAVE;
     if (use_vrows() && use_vrows_pair() && dwconv_mfma_wgrad_vrows_supported(d, dtype, dtype)) return PAIR_WGRAD_VROWS;
     return PAIR_WGRAD_NONE;
@@ -383,7 +386,7 @@ int slak_dwconv2d_pair_backward_filter(const void* dy_v, const void* dy_s, const
     if (!dy_v || !dy_s || !x || !dw_v || !dw_s) return SLAK_ERR_INVALID_ARG;
     if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || K <= 5) return SLAK_ERR_INVALID_ARG;
     ConvDims d{N, C, H, W, K, MF_TAPS_HOST};
-    if (g_conv_algo == SLAK_ALGO_DIRECT || !use_dma()) return SLAK_ERR_UNSUPPORTED;
+    if (g_conv_algo == SLAK_ALGO_DIRECT) return SLAK_ERR_UNSUPPORTED;
     switch (pair_wgrad_kernel(d, dtype)) {
         case PAIR_WGRAD_VWAVE: return SLAK_RAN("dwconv_mfma_wgrad_vwave(pair)", launch_dwconv_mfma_wgrad_vwave(dy_v, dtype, x, dtype, dw_v, d, workspace, workspace_bytes, (hipStream_t)stream, dy_s, dw_s));
         case PAIR_WGRAD_VROWS: return SLAK_RAN("dwconv_mfma_wgrad_vrows(pair)", launch_dwconv_mfma_wgrad_vrows(dy_v, dtype, x, dtype, dw_v, d, workspace, workspace_bytes, (hipStream_t)stream, dy_s, dw_s));

@@ -260,6 +260,10 @@ int launch_dwconv_wgrad(const void* dy, int dy_dt, const void* x, int x_dt, floa
     return launch_wgrad_reduce((const float*)ws, dw, d.C * d.kh * d.kw, p.nslices, st);
 }
 
+// SLAK_WGRAD_REDUCE=1: partials + a separate reduce launch (A/B and debugging).  The kernels that have no such variant (the three-branch, pair and
+// one-launch-backward weight gradients) do not exist then: their size / support queries in capi.hip ask this too, so that they and the launches agree.
+bool wgrad_reduce_forced() { static const bool v = slak_env_flag("SLAK_WGRAD_REDUCE", false); return v; }
+
 unsigned* wgrad_arrival_counters(int ngroups) {
     // SLOTS launches may be in flight at once before a slot's counters are handed out again (a stream serialises its own launches;
     // the slots only matter for weight-gradient launches running concurrently on different streams)
@@ -268,8 +272,7 @@ unsigned* wgrad_arrival_counters(int ngroups) {
     static unsigned* buf[MAXDEV] = {};
     static unsigned next[MAXDEV] = {};
     if (ngroups > MAXG) return nullptr;
-    static const bool force_reduce = slak_env_flag("SLAK_WGRAD_REDUCE", false);
-    if (force_reduce) return nullptr;                 // SLAK_WGRAD_REDUCE=1: partials + a separate reduce launch (A/B and debugging)
+    if (wgrad_reduce_forced()) return nullptr;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAXDEV) return nullptr;
     std::lock_guard<std::mutex> lk(mu);

@@ -205,6 +205,7 @@ int launch_dwconv_mfma_wgrad(const void* dy, int dy_dt, const void* x, int x_dt,
 // counter; the last arriver adds the nslices partials in slice order (bitwise reproducible: the same order whichever
 // workgroup happens to be last) and writes dw.  Counters come zeroed from wgrad_arrival_counters() and the last arriver
 // puts its counter back to zero, so a launch leaves them as it found them.
+bool wgrad_reduce_forced();                         // host; SLAK_WGRAD_REDUCE=1: wgrad_arrival_counters() hands out none
 unsigned* wgrad_arrival_counters(int ngroups);      // host; nullptr -> use launch_wgrad_reduce() after the kernel instead
 #if defined(__HIPCC__)
 // partial stores go through wgrad_store_partial(): written through to the device coherence point (agent-scope atomic store),

@@ -7,6 +7,10 @@
                                                       shapes with each switch of QUERY_SWITCHES off -> tests/golden/dispatch_queries.npz
     python tools/print_dispatch.py --mlp              slak_mlp_plan for the pointwise MLP of every stage of the configurations (host code only)
     python tools/print_dispatch.py --stage-queries    (what --queries runs in a child process per switch: switches are read once per process)
+    python tools/print_dispatch.py --switches OUT.json  the launches of the small shapes (--small) in one child process per conv A/B switch
+                                                      of tests/ab_switches.py's SWITCHES, the switch at its flip value: per switch the keys whose family differs from
+                                                      dispatch_table_small.json (needs the GPU; without one that part of OUT.json is kept as it is); per block-tail switch what
+                                                      slak_block_tail_family answers in a DEFAULT process on the switch's shapes (host code) -> tests/golden/dispatch_table_switches.json
 
 tests/test_dispatch_gpu.py and tests/test_dispatch_queries.py load table(), small_shapes(), queries() from this file by path."""
 import ctypes
@@ -38,8 +42,9 @@ def benchmark_shapes():
 
 def small_shapes():
     """Only shapes the parity tests already launch (no kernel meets a shape here that it has not met there)."""
-    if ROOT not in sys.path:
-        sys.path.insert(0, ROOT)                    # the test modules import the oracle package
+    for p in (os.path.join(ROOT, "tests"), ROOT):    # the test modules import the oracle package and their shared helpers (tests/conv_calls.py)
+        if p not in sys.path:
+            sys.path.insert(0, p)
     fused, mfma = _load("tests/test_fused_launches_gpu.py", "_fused_shapes"), _load("tests/test_mfma_gpu.py", "_mfma_shapes")
     blocks = fused.TRI_SMALL + fused.TRI_WIDE + fused.TRI_BWD + fused.TRI_WAVE + fused.PAIR_SMALL + [s for s in fused.TRI_ROWS if s[0] <= 9]
     blocks = [("n%d_c%d_%dx%d_k%d" % s,) + s for s in dict.fromkeys(blocks)]
@@ -137,6 +142,32 @@ def all_queries():
     return out
 
 
+def switch_tables(path):
+    """What tests/golden/dispatch_table_switches.json holds: {conv switch: {key: family}} over the keys of table(small_shapes()) whose family a process with
+    the switch flipped (SWITCHES' flip value: "1" for a default-off switch) reports differently from tests/golden/dispatch_table_small.json (None: the launch is
+    gone), and {block-tail switch: {shape: {op: family}}} as a DEFAULT process answers."""
+    ab = _load("tests/ab_switches.py", "_ab_switches")
+    out = json.load(open(path)) if os.path.exists(path) else {}
+    lib = _load("slak_amd/_lib.py", "_slak_lib_only")
+    for name, sw in ab.SWITCHES.items():
+        assert name not in os.environ, name + " is set: the default answers need a default process"
+        if sw["group"] == "tail":
+            out[name] = {ab.tail_key(c): ab.tail_families(lib.lib(), lib, c) for c in sw["cases"]}
+    import torch
+    if torch.cuda.is_available():
+        small = json.load(open(os.path.join(ROOT, "tests", "golden", "dispatch_table_small.json")))
+        for name in ab.CONV_SWITCHES:
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--small"], env=dict(os.environ, **{name: ab.SWITCHES[name]["flip"]}), check=True,
+                               stdout=subprocess.PIPE, timeout=300)
+            out[name] = ab.table_diff(small, json.loads(r.stdout))
+            print(name, len(out[name]), "keys differ", file=sys.stderr)
+    else:
+        print("no GPU: the conv switches' tables are left as they are", file=sys.stderr)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=0, sort_keys=True)
+        f.write("\n")
+
+
 def mlp_plans():
     """{stage: {step: rung}}: slak_mlp_plan (allow = every kernel family) for the pointwise MLP of every stage of CONFIGS.  Host code only."""
     lib = _load("slak_amd/_lib.py", "_slak_lib_only")
@@ -152,6 +183,8 @@ def mlp_plans():
 if __name__ == "__main__":
     if "--mlp" in sys.argv:
         print(json.dumps(mlp_plans(), indent=0))
+    elif "--switches" in sys.argv:
+        switch_tables(sys.argv[sys.argv.index("--switches") + 1])
     elif "--stage-queries" in sys.argv:
         print(json.dumps(queries(load_lib(), STAGE_POINTS)))
     elif "--queries" in sys.argv:
