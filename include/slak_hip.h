@@ -59,7 +59,7 @@ const char* slak_last_hip_error(void);      /* text of the last HIP error seen b
 /* ABI version: bumped whenever an entry point's argument list or meaning changes (round 5: 5).  A host module compiled against this header
  * (slak_amd/pybind, *.cpp) records the value it saw and refuses to load on a library that reports another one: a stale module would call raw-pointer
  * entry points with a changed argument list -- silent corruption, not an error. */
-#define SLAK_ABI_VERSION 9
+#define SLAK_ABI_VERSION 10
 int slak_version(void);                     /* == SLAK_ABI_VERSION of the header the library was built from */
 int slak_device_info(int* cu_count, int* lds_bytes_per_cu, char* arch_name, size_t arch_name_len);
 int slak_set_conv_algo(int algo);           /* process-wide override of the AUTO choice */
@@ -213,6 +213,43 @@ int slak_dwconv2d_tri_backward(const void* dy_v, const void* dy_h, const void* d
 size_t slak_dwconv2d_pair_filter_workspace_bytes(int dtype, int N, int C, int H, int W, int K);
 int slak_dwconv2d_pair_backward_filter(const void* dy_v, const void* dy_s, const void* x, float* dw_v, float* dw_s,
                                        int dtype, int N, int C, int H, int W, int K, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Which entry point runs each step of a block's three branch convs (forward, summed data gradient, the three weight gradients) on an (N,C,H,W) input
+ * with a K x 5, a 5 x K and a 5 x 5 filter.  The ONE place where the ladder is written: every field takes the first rung, in the order listed, that
+ * the queries above support and `allow` admits.  Pure host code, built from slak_dwconv2d_tri_supported_op, _tri_stats_rows,
+ * _tri_filter_workspace_bytes, _pair_filter_workspace_bytes and _tri_backward_supported and nothing else (capi.hip decides which KERNEL exists; this
+ * decides which ENTRY POINT a block calls).  Both callers (slak_amd/block_ops.py, slak_amd/pybind/block_runner.cpp) switch on the answer.
+ *   fwd    TRI_STATS    slak_dwconv2d_tri_forward_stats: FUSED, supported_op(.., 0), STATS and stats_rows > 0
+ *          TRI          slak_dwconv2d_tri_forward: FUSED and supported_op(.., 0)
+ *          BRANCH_STATS three slak_dwconv2d_forward_stats (each falls back to slak_dwconv2d_forward where no kernel gathers sums): STATS
+ *          BRANCH       three slak_dwconv2d_forward
+ *   stats_rows  rows of the [rows][C][6] array of TRI_STATS, else 0
+ *   dgrad  ONE          slak_dwconv2d_tri_backward (the weight gradients are in the same launch: wgrad is ONE too) -- FUSED, WGRAD and BACKWARD,
+ *                       tri filter workspace bytes > 0 and slak_dwconv2d_tri_backward_supported
+ *          TRI          slak_dwconv2d_tri_backward_data: FUSED and supported_op(.., 1)
+ *          BRANCH_ACC   slak_dwconv2d_backward_data, then two slak_dwconv2d_backward_data_accumulate: DGRAD_ACC
+ *          BRANCH_ADD   three slak_dwconv2d_backward_data and two tensor adds
+ *   wgrad  ONE          (with dgrad)
+ *          TRI          slak_dwconv2d_tri_backward_filter: WGRAD and tri filter workspace bytes > 0
+ *          PAIR         slak_dwconv2d_pair_backward_filter + slak_dwconv2d_backward_filter for 5 x K: WGRAD and pair filter workspace bytes > 0
+ *          BRANCH       three slak_dwconv2d_backward_filter
+ *   ws_wgrad    workspace bytes of the chosen ONE / TRI / PAIR launch, else 0
+ * The plan describes a backward that needs all four gradients; a call that needs fewer steps down on its own (ONE: dx and the three dw; TRI wgrad: the
+ * three dw; PAIR: dw_v and dw_s).  A launch may still answer SLAK_ERR_UNSUPPORTED after the plan named it (slak_set_conv_algo can change in between and
+ * the pair launch honours it; the device's CU count decides the three-branch weight gradient's work split): the caller then drops one rung.
+ * allow: SLAK_TRI_ALLOW_FUSED (the launches that READ the three fp32 filters: TRI_STATS / TRI forward, TRI data gradient, ONE; a caller whose filters
+ * are not contiguous fp32 clears it) | _STATS (gather the BatchNorm sums in the forward launches) | _WGRAD (the TRI and PAIR weight gradients) |
+ * _BACKWARD (ONE) | _DGRAD_ACC (BRANCH_ACC).  SLAK_ERR_INVALID_ARG: plan == NULL or a dimension <= 0. */
+enum { SLAK_TRI_FWD_BRANCH = 0, SLAK_TRI_FWD_BRANCH_STATS = 1, SLAK_TRI_FWD_TRI = 2, SLAK_TRI_FWD_TRI_STATS = 3 };
+enum { SLAK_TRI_DGRAD_BRANCH_ADD = 0, SLAK_TRI_DGRAD_BRANCH_ACC = 1, SLAK_TRI_DGRAD_TRI = 2, SLAK_TRI_DGRAD_ONE = 3 };
+enum { SLAK_TRI_WGRAD_BRANCH = 0, SLAK_TRI_WGRAD_PAIR = 1, SLAK_TRI_WGRAD_TRI = 2, SLAK_TRI_WGRAD_ONE = 3 };
+enum { SLAK_TRI_ALLOW_FUSED = 1, SLAK_TRI_ALLOW_STATS = 2, SLAK_TRI_ALLOW_WGRAD = 4, SLAK_TRI_ALLOW_BACKWARD = 8, SLAK_TRI_ALLOW_DGRAD_ACC = 16,
+       SLAK_TRI_ALLOW_ALL = 31 };
+typedef struct slak_tri_plan {
+    int fwd, stats_rows, dgrad, wgrad;
+    size_t ws_wgrad;
+} slak_tri_plan_t;
+int slak_tri_plan(int dtype, int N, int C, int H, int W, int K, unsigned allow, slak_tri_plan_t* plan);
 
 /* ---------------------------------------------------------------- next row: block tail glue
  * The layout / normalisation / residual steps around the two pointwise GEMMs of a SLaK block

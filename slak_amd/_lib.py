@@ -54,6 +54,10 @@ class MlpPlan(ctypes.Structure):                                     # slak_mlp_
     _fields_ = [(n, ctypes.c_int) for n in ("pw1", "pw2", "dy1", "dt", "dw1", "dw2", "splits")] + [(n, ctypes.c_size_t) for n in ("ws_dy1", "ws_dw1", "ws_dw2")]
 
 
+class TriPlan(ctypes.Structure):                                     # slak_tri_plan_t: the rung of every step of a block's three branch convs (include/slak_hip.h)
+    _fields_ = [(n, ctypes.c_int) for n in ("fwd", "stats_rows", "dgrad", "wgrad")] + [("ws_wgrad", ctypes.c_size_t)]
+
+
 # name -> (restype, argtypes): every symbol include/slak_hip.h declares (tests/test_boundary.py checks this)
 _vp, _i, _sz, _d = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_double
 _CONV = [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]
@@ -131,6 +135,7 @@ SIGNATURES = {
     "slak_dwconv2d_pair_filter_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "slak_dwconv2d_pair_backward_filter": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "slak_dwconv2d_tri_backward_filter": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "slak_tri_plan": (_i, [_i, _i, _i, _i, _i, _i, ctypes.c_uint, ctypes.POINTER(TriPlan)]),   # (dtype, N, C, H, W, K, allow, plan); host only
     "slak_stem_patchify": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "slak_stem_conv_forward_supported": (_i, [_i, _i, _i, _i, _i]),
     "slak_stem_conv_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
@@ -193,6 +198,14 @@ TAIL_FAMILY_NAMES = ("none", "tile", "reg", "chan", "chan1")
 MLP_LIBRARY, MLP_NT, MLP_GEMM, MLP_FUSED, MLP_FUSED_DT, MLP_KERNEL = 0, 1, 2, 3, 4, 5
 MLP_RUNG_NAMES = ("library", "nt", "gemm", "fused", "fused_dt", "kernel")
 MLP_ALLOW_SKINNY, MLP_ALLOW_GEMM, MLP_ALLOW_WGRAD, MLP_ALLOW_ALL = 1, 2, 4, 7
+# slak_tri_plan: the rungs of each field and the `allow` mask (include/slak_hip.h)
+TRI_FWD_BRANCH, TRI_FWD_BRANCH_STATS, TRI_FWD_TRI, TRI_FWD_TRI_STATS = 0, 1, 2, 3
+TRI_DGRAD_BRANCH_ADD, TRI_DGRAD_BRANCH_ACC, TRI_DGRAD_TRI, TRI_DGRAD_ONE = 0, 1, 2, 3
+TRI_WGRAD_BRANCH, TRI_WGRAD_PAIR, TRI_WGRAD_TRI, TRI_WGRAD_ONE = 0, 1, 2, 3
+TRI_FWD_NAMES = ("branch", "branch_stats", "tri", "tri_stats")
+TRI_DGRAD_NAMES = ("branch_add", "branch_acc", "tri", "one")
+TRI_WGRAD_NAMES = ("branch", "pair", "tri", "one")
+TRI_ALLOW_FUSED, TRI_ALLOW_STATS, TRI_ALLOW_WGRAD, TRI_ALLOW_BACKWARD, TRI_ALLOW_DGRAD_ACC, TRI_ALLOW_ALL = 1, 2, 4, 8, 16, 31
 
 
 def lib():

@@ -5,7 +5,6 @@
 
 (models/SLaK.py:153-166, :253-255).  x bf16 NCHW, z bf16 NHWC; parameters, statistics and the residual stream fp32.
 """
-import collections
 import ctypes
 import os
 
@@ -167,32 +166,37 @@ class _ScaleResidual(torch.autograd.Function):
 accumulate_dgrad = os.environ.get("SLAK_DGRAD_ACC", "1") != "0"     # A/B switch: 0 = three plain launches + two tensor adds
 fused_tri_wgrad = os.environ.get("SLAK_TRI_WGRAD", "1") != "0"      # A/B switch: 0 = three weight-gradient launches per block everywhere
 fused_tri_backward = os.environ.get("SLAK_TRI_BACKWARD", "1") != "0"   # A/B switch: 0 = the data-gradient launch and the weight-gradient launch apart on the 14 x 14 class as well
+bn_stats_in_conv = os.environ.get("SLAK_BN_STATS_IN_CONV", "1") != "0"   # three-branch forward launches also leave the branch BatchNorms' batch sums
 
 
+# The branch convs' launch ladder is written once, in the library (slak_tri_plan, include/slak_hip.h): _tri_forward_impl and _tri_backward_impl ask for
+# the plan and switch on it -- as slak_amd/pybind/block_runner.cpp does on the same plan.  The four switches above are bits of its `allow` mask.
 _tri_plan_cache = {}
-# one-launch forward?  one-launch data gradient?  rows of the forward launch's BatchNorm statistics; workspace bytes of the three-branch weight
-# gradient and of the two-branch one (0: no such launch); data gradient + the three weight gradients in one launch?
-_TriPlan = collections.namedtuple("_TriPlan", "forward dgrad stats_rows tri_wgrad_bytes pair_wgrad_bytes backward")
-_NO_TRI_PLAN = _TriPlan(False, False, 0, 0, 0, False)
 
 
-def _tri_plan(dt, N, C, H, W, K):
-    """What the library answers for a block shape, asked once per (dtype, shape): six ctypes calls per block and direction otherwise."""
-    key = (dt, N, C, H, W, K)
+def _tri_allow(wv, wh, ws, want_stats):
+    """slak_tri_plan's `allow` mask: the four switches above, read at call time, and what the call itself knows -- the launches that read the three
+    filters need them as contiguous fp32, and the BatchNorm sums are gathered only for a caller that takes them (want_stats == 2)."""
+    f32w = all(w.dtype == torch.float32 and w.is_contiguous() for w in (wv, wh, ws))
+    return ((_lib.TRI_ALLOW_FUSED if f32w else 0) | (_lib.TRI_ALLOW_STATS if (bn_stats_in_conv and want_stats == 2) else 0) |
+            (_lib.TRI_ALLOW_WGRAD if fused_tri_wgrad else 0) | (_lib.TRI_ALLOW_BACKWARD if fused_tri_backward else 0) |
+            (_lib.TRI_ALLOW_DGRAD_ACC if accumulate_dgrad else 0))
+
+
+def _tri_plan(dt, N, C, H, W, K, allow):
+    """slak_tri_plan's answer for a block shape, asked once per (dtype, shape, allow)."""
+    key = (dt, N, C, H, W, K, allow)
     plan = _tri_plan_cache.get(key)
     if plan is None:
-        L = _lib.lib()
-        plan = _TriPlan(L.slak_dwconv2d_tri_supported_op(dt, N, C, H, W, K, 0) == 1, L.slak_dwconv2d_tri_supported_op(dt, N, C, H, W, K, 1) == 1,
-                        int(L.slak_dwconv2d_tri_stats_rows(dt, N, C, H, W, K)), int(L.slak_dwconv2d_tri_filter_workspace_bytes(dt, N, C, H, W, K)),
-                        int(L.slak_dwconv2d_pair_filter_workspace_bytes(dt, N, C, H, W, K)),
-                        L.slak_dwconv2d_tri_backward_supported(dt, N, C, H, W, K) == 1)
+        plan = _lib.TriPlan()
+        _lib.check(_lib.lib().slak_tri_plan(dt, N, C, H, W, K, allow, ctypes.byref(plan)), "slak_tri_plan")
         _tri_plan_cache[key] = plan
     return plan
 
 
 def _tri_forward_impl(x, wv, wh, ws, want_stats):
-    """-> (yv, yh, ys, stats, tri_dgrad): the three branch outputs, the BatchNorm sums the launch(es) gathered (one [rows][C][6] array, a triple
-    of [rows_b][C][2] arrays, or None) and whether the one-launch data gradient exists for this shape."""
+    """-> (yv, yh, ys, stats, allow): the three branch outputs, the BatchNorm sums the launch(es) gathered (one [rows][C][6] array, a triple
+    of [rows_b][C][2] arrays, or None) and the slak_tri_plan mask this forward asked with (the backward asks with the same)."""
     from . import ops
     _chk(x, "input")
     N, C, H, W = x.shape
@@ -200,18 +204,15 @@ def _tri_forward_impl(x, wv, wh, ws, want_stats):
     if wv.shape != (C, 1, K, 5) or wh.shape != (C, 1, 5, K) or ws.shape != (C, 1, 5, 5):
         raise RuntimeError("tri_dwconv expects filters (C,1,K,5), (C,1,5,K), (C,1,5,5)")
     L = _lib.lib()
-    dt = ops._DT.get(x.dtype)
-    # one launch for the three branches where the library says it wins (slak_dwconv2d_tri_supported_op: per op)
-    f32w = all(w.dtype == torch.float32 and w.is_contiguous() for w in (wv, wh, ws))
-    plan = _tri_plan(dt, N, C, H, W, K) if (dt is not None and f32w) else _NO_TRI_PLAN
-    tri, tri_dgrad = plan.forward, plan.dgrad
+    dt = ops._dt(x, "input")
+    allow = _tri_allow(wv, wh, ws, want_stats)
+    plan = _tri_plan(dt, N, C, H, W, K, allow)
     stats = None
-    if tri:
+    if plan.fwd in (_lib.TRI_FWD_TRI_STATS, _lib.TRI_FWD_TRI):   # one launch for the three branches where the library says it wins
         yv, yh, ys = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
-        rows = plan.stats_rows if (want_stats == 2 and bn_stats_in_conv) else 0
         with _on(x.device):
-            if rows > 0:                                     # the launch also leaves the branch BatchNorms' batch statistics
-                stats = torch.empty((rows, C, 6), dtype=torch.float32, device=x.device)
+            if plan.fwd == _lib.TRI_FWD_TRI_STATS:              # the launch also leaves the branch BatchNorms' batch statistics
+                stats = torch.empty((plan.stats_rows, C, 6), dtype=torch.float32, device=x.device)
                 _lib.check(L.slak_dwconv2d_tri_forward_stats(x.data_ptr(), wv.data_ptr(), wh.data_ptr(), ws.data_ptr(), yv.data_ptr(),
                                                              yh.data_ptr(), ys.data_ptr(), stats.data_ptr(), dt, N, C, H, W, K, _stream(x.device)),
                            "slak_dwconv2d_tri_forward_stats")
@@ -219,85 +220,80 @@ def _tri_forward_impl(x, wv, wh, ws, want_stats):
                 _lib.check(L.slak_dwconv2d_tri_forward(x.data_ptr(), wv.data_ptr(), wh.data_ptr(), ws.data_ptr(), yv.data_ptr(),
                                                        yh.data_ptr(), ys.data_ptr(), dt, N, C, H, W, K, _stream(x.device)),
                            "slak_dwconv2d_tri_forward")
-    elif want_stats == 2 and bn_stats_in_conv:               # per-branch launches that gather their BatchNorm's sums in the copy-out
+    elif plan.fwd == _lib.TRI_FWD_BRANCH_STATS:                 # per-branch launches that gather their BatchNorm's sums in the copy-out
         (yv, sv), (yh, sh), (ys, ss) = ops.dwconv2d_forward_stats(x, wv), ops.dwconv2d_forward_stats(x, wh), ops.dwconv2d_forward_stats(x, ws)
         if sv is not None and sh is not None and ss is not None:
             stats = (sv, sh, ss)
     else:
         yv, yh, ys = ops.dwconv2d_forward(x, wv), ops.dwconv2d_forward(x, wh), ops.dwconv2d_forward(x, ws)
-    return yv, yh, ys, stats, tri_dgrad
+    return yv, yh, ys, stats, allow
 
 
-def _tri_backward_impl(x, wv, wh, ws, dyv, dyh, dys, tri_dgrad, need_dx, need_w):
-    """-> (dx, dwv, dwh, dws); need_w: three booleans."""
+def _tri_backward_impl(x, wv, wh, ws, dyv, dyh, dys, allow, need_dx, need_w):
+    """-> (dx, dwv, dwh, dws); allow: the forward's slak_tri_plan mask; need_w: three booleans.  The plan describes a backward that needs all four
+    gradients: a call that needs fewer steps down here, and so does a launch that answers SLAK_ERR_UNSUPPORTED after the plan named it
+    (slak_set_conv_algo may have changed in between) -- one rung each time."""
     from . import ops
     N, C, H, W = x.shape
     K = wv.shape[2]
     dyv, dyh, dys = (torch.zeros_like(x) if g is None else g for g in (dyv, dyh, dys))       # (a branch output nobody used)
     dyv, dyh, dys = (g.contiguous() if g.dtype == x.dtype else g.to(x.dtype).contiguous() for g in (dyv, dyh, dys))
-    dx = None
-    plan = _tri_plan(ops._DT[x.dtype], N, C, H, W, K) if x.dtype in ops._DT else _NO_TRI_PLAN
-    if need_dx and all(need_w) and fused_tri_wgrad and fused_tri_backward and plan.backward and plan.tri_wgrad_bytes and \
-            all(w.dtype == torch.float32 and w.is_contiguous() for w in (wv, wh, ws)):
-        # the whole backward in ONE launch (14 x 14 class): the dY planes are staged once for dx and for the three weight gradients
-        L = _lib.lib()
-        dx = torch.empty_like(x)
-        dwv, dwh, dws = (torch.empty_like(w, dtype=torch.float32) for w in (wv, wh, ws))
-        wsb, nbb = _workspace(plan.tri_wgrad_bytes, x.device)
-        with _on(x.device):
-            rc = L.slak_dwconv2d_tri_backward(dyv.data_ptr(), dyh.data_ptr(), dys.data_ptr(), x.data_ptr(), wv.data_ptr(), wh.data_ptr(), ws.data_ptr(),
-                                              dx.data_ptr(), dwv.data_ptr(), dwh.data_ptr(), dws.data_ptr(), ops._DT[x.dtype], N, C, H, W, K,
-                                              wsb.data_ptr(), nbb, _stream(x.device))
-        if rc != _lib.ERR_UNSUPPORTED:
-            _lib.check(rc, "slak_dwconv2d_tri_backward")
-            return dx, dwv, dwh, dws
-        dx = None
-    if need_dx:
-        if tri_dgrad:
+    L = _lib.lib()
+    dt = ops._DT[x.dtype]
+    plan = _tri_plan(dt, N, C, H, W, K, allow)
+    if plan.dgrad == _lib.TRI_DGRAD_ONE:
+        if need_dx and all(need_w):
+            # the whole backward in ONE launch (14 x 14 class): the dY planes are staged once for dx and for the three weight gradients
             dx = torch.empty_like(x)
-            L = _lib.lib()
+            dwv, dwh, dws = (torch.empty_like(w, dtype=torch.float32) for w in (wv, wh, ws))
+            wsb, nbb = _workspace(plan.ws_wgrad, x.device)
             with _on(x.device):
-                _lib.check(L.slak_dwconv2d_tri_backward_data(dyv.data_ptr(), dyh.data_ptr(), dys.data_ptr(), wv.data_ptr(),
-                                                             wh.data_ptr(), ws.data_ptr(), dx.data_ptr(), ops._DT[x.dtype],
-                                                             N, C, H, W, K, _stream(x.device)), "slak_dwconv2d_tri_backward_data")
-        else:
-            dx = ops.dwconv2d_backward_data(dyv, wv)
-            if accumulate_dgrad:
-                ops.dwconv2d_backward_data_accumulate(dyh, wh, dx)   # autograd's two adds folded into the kernels' copy-out
-                ops.dwconv2d_backward_data_accumulate(dys, ws, dx)
-            else:
-                dx += ops.dwconv2d_backward_data(dyh, wh)
-                dx += ops.dwconv2d_backward_data(dys, ws)
-    dwv = dwh = dws = None
-    if all(need_w) and fused_tri_wgrad and plan.tri_wgrad_bytes:          # one launch for the three weight gradients (x fetched once)
-        L = _lib.lib()
-        dt = ops._DT[x.dtype]
-        dwv, dwh, dws = (torch.empty_like(w, dtype=torch.float32) for w in (wv, wh, ws))
-        wsb, nbb = _workspace(plan.tri_wgrad_bytes, x.device)
+                rc = L.slak_dwconv2d_tri_backward(dyv.data_ptr(), dyh.data_ptr(), dys.data_ptr(), x.data_ptr(), wv.data_ptr(), wh.data_ptr(), ws.data_ptr(),
+                                                  dx.data_ptr(), dwv.data_ptr(), dwh.data_ptr(), dws.data_ptr(), dt, N, C, H, W, K,
+                                                  wsb.data_ptr(), nbb, _stream(x.device))
+            if rc != _lib.ERR_UNSUPPORTED:
+                _lib.check(rc, "slak_dwconv2d_tri_backward")
+                return dx, dwv, dwh, dws
+        plan = _tri_plan(dt, N, C, H, W, K, allow & ~_lib.TRI_ALLOW_BACKWARD)     # the data-gradient launch and the weight-gradient launch apart
+    dx = None
+    if need_dx and plan.dgrad == _lib.TRI_DGRAD_TRI:
+        dx = torch.empty_like(x)
         with _on(x.device):
-            rc = L.slak_dwconv2d_tri_backward_filter(dyv.data_ptr(), dyh.data_ptr(), dys.data_ptr(), x.data_ptr(), dwv.data_ptr(),
-                                                     dwh.data_ptr(), dws.data_ptr(), dt, N, C, H, W, K, wsb.data_ptr(), nbb, _stream(x.device))
-        if rc == _lib.ERR_UNSUPPORTED:
-            dwv = dwh = dws = None
+            _lib.check(L.slak_dwconv2d_tri_backward_data(dyv.data_ptr(), dyh.data_ptr(), dys.data_ptr(), wv.data_ptr(), wh.data_ptr(), ws.data_ptr(),
+                                                         dx.data_ptr(), dt, N, C, H, W, K, _stream(x.device)), "slak_dwconv2d_tri_backward_data")
+    elif need_dx:
+        dx = ops.dwconv2d_backward_data(dyv, wv)
+        if plan.dgrad == _lib.TRI_DGRAD_BRANCH_ACC:
+            ops.dwconv2d_backward_data_accumulate(dyh, wh, dx)   # autograd's two adds folded into the kernels' copy-out
+            ops.dwconv2d_backward_data_accumulate(dys, ws, dx)
         else:
-            _lib.check(rc, "slak_dwconv2d_tri_backward_filter")
-    if dwv is None and need_w[0] and need_w[2] and fused_tri_wgrad and plan.pair_wgrad_bytes:      # K x 5 and 5 x 5 in one launch (x fetched and shifted once)
-        L = _lib.lib()
-        dt = ops._DT[x.dtype]
+            dx += ops.dwconv2d_backward_data(dyh, wh)
+            dx += ops.dwconv2d_backward_data(dys, ws)
+    wgrad, nbytes = plan.wgrad, plan.ws_wgrad
+    if wgrad == _lib.TRI_WGRAD_TRI:
+        if all(need_w):                                          # one launch for the three weight gradients (x fetched once)
+            dwv, dwh, dws = (torch.empty_like(w, dtype=torch.float32) for w in (wv, wh, ws))
+            wsb, nbb = _workspace(nbytes, x.device)
+            with _on(x.device):
+                rc = L.slak_dwconv2d_tri_backward_filter(dyv.data_ptr(), dyh.data_ptr(), dys.data_ptr(), x.data_ptr(), dwv.data_ptr(),
+                                                         dwh.data_ptr(), dws.data_ptr(), dt, N, C, H, W, K, wsb.data_ptr(), nbb, _stream(x.device))
+            if rc != _lib.ERR_UNSUPPORTED:
+                _lib.check(rc, "slak_dwconv2d_tri_backward_filter")
+                return dx, dwv, dwh, dws
+        nbytes = int(L.slak_dwconv2d_pair_filter_workspace_bytes(dt, N, C, H, W, K))     # the rung below, which the plan's TRI shadows
+        wgrad = _lib.TRI_WGRAD_PAIR if nbytes else _lib.TRI_WGRAD_BRANCH
+    if wgrad == _lib.TRI_WGRAD_PAIR and need_w[0] and need_w[2]:    # K x 5 and 5 x 5 in one launch (x fetched and shifted once)
         dwv, dws = (torch.empty_like(w, dtype=torch.float32) for w in (wv, ws))
-        wsb, nbb = _workspace(plan.pair_wgrad_bytes, x.device)
+        wsb, nbb = _workspace(nbytes, x.device)
         with _on(x.device):
             rc = L.slak_dwconv2d_pair_backward_filter(dyv.data_ptr(), dys.data_ptr(), x.data_ptr(), dwv.data_ptr(), dws.data_ptr(),
                                                       dt, N, C, H, W, K, wsb.data_ptr(), nbb, _stream(x.device))
-        if rc == _lib.ERR_UNSUPPORTED:
-            dwv = dws = None
-        else:
+        if rc != _lib.ERR_UNSUPPORTED:
             _lib.check(rc, "slak_dwconv2d_pair_backward_filter")
-            dwh = ops.dwconv2d_backward_filter(dyh, x, wh) if need_w[1] else None
-    if dwv is None:
-        dwv = ops.dwconv2d_backward_filter(dyv, x, wv) if need_w[0] else None
-        dwh = ops.dwconv2d_backward_filter(dyh, x, wh) if need_w[1] else None
-        dws = ops.dwconv2d_backward_filter(dys, x, ws) if need_w[2] else None
+            return dx, dwv, ops.dwconv2d_backward_filter(dyh, x, wh) if need_w[1] else None, dws
+    dwv = ops.dwconv2d_backward_filter(dyv, x, wv) if need_w[0] else None
+    dwh = ops.dwconv2d_backward_filter(dyh, x, wh) if need_w[1] else None
+    dws = ops.dwconv2d_backward_filter(dys, x, ws) if need_w[2] else None
     return dx, dwv, dwh, dws
 
 
@@ -309,7 +305,7 @@ class _TriDwConv(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, wv, wh, ws, want_stats=False):
-        yv, yh, ys, stats, ctx.tri_dgrad = _tri_forward_impl(x, wv, wh, ws, want_stats)
+        yv, yh, ys, stats, ctx.tri_allow = _tri_forward_impl(x, wv, wh, ws, want_stats)
         ctx.save_for_backward(x, wv, wh, ws)
         # (the three statistics outputs are non-differentiable; autograd would still hand backward() a ZERO tensor for each of them --
         # three fill launches per block and step, 54 of the 56 FillFunctor launches of a SLaK-T step)
@@ -325,7 +321,7 @@ class _TriDwConv(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dyv, dyh, dys, *_dstats):
         x, wv, wh, ws = ctx.saved_tensors
-        dx, dwv, dwh, dws = _tri_backward_impl(x, wv, wh, ws, dyv, dyh, dys, ctx.tri_dgrad, ctx.needs_input_grad[0], ctx.needs_input_grad[1:4])
+        dx, dwv, dwh, dws = _tri_backward_impl(x, wv, wh, ws, dyv, dyh, dys, ctx.tri_allow, ctx.needs_input_grad[0], ctx.needs_input_grad[1:4])
         return dx, dwv, dwh, dws, None
 
 
@@ -336,9 +332,6 @@ def _stats_triple(stats, device):
     if not isinstance(stats, tuple):
         return (stats, stats[:, :, 2:], stats[:, :, 4:])
     return stats
-
-
-bn_stats_in_conv = os.environ.get("SLAK_BN_STATS_IN_CONV", "1") != "0"   # three-branch forward launches also leave the branch BatchNorms' batch sums
 
 
 def tri_dwconv(x, w_vertical, w_horizontal, w_small, want_stats=False):
@@ -360,10 +353,10 @@ def tri_dwconv_sum(x, w_vertical, w_horizontal, w_small, bias=None):
         N, C, H, W = x.shape
         K = w_vertical.shape[2]
         L = _lib.lib()
-        dt = ops._DT.get(x.dtype)
+        dt = ops._dt(x, "input")
         ws = [w.detach().float().contiguous() for w in (w_vertical, w_horizontal, w_small)]
-        if (dt is not None and ws[0].shape == (C, 1, K, 5) and ws[1].shape == (C, 1, 5, K) and ws[2].shape == (C, 1, 5, 5)
-                and L.slak_dwconv2d_tri_supported_op(dt, N, C, H, W, K, 1) == 1):      # (it IS the data-gradient kernel: same policy as the training node)
+        if (ws[0].shape == (C, 1, K, 5) and ws[1].shape == (C, 1, 5, K) and ws[2].shape == (C, 1, 5, 5)       # (it IS the data-gradient kernel: the training
+                and _tri_plan(dt, N, C, H, W, K, _lib.TRI_ALLOW_FUSED).dgrad == _lib.TRI_DGRAD_TRI):           # node's rung, without the one-launch backward)
             fl = [w.flip(2, 3).contiguous() for w in ws]
             y = torch.empty_like(x)
             with _on(x.device):
@@ -1431,10 +1424,9 @@ _force_bn_exchange = os.environ.get("SLAK_FORCE_BN_EXCHANGE", "0") == "1"   # be
 
 
 def _runner_switches():
-    """The development switches that select paths only the Python sequence knows: with any of them off their default the runner steps aside, so an
-    A/B run measures what its switch says.  Read on every call: a test may flip a switch after the first block has run.
-    (The MLP's switches are not among them: the runner follows slak_mlp_plan under the same `allow` mask as the Python sequence.)"""
-    return (fused_tri_backward and fused_tri_wgrad and bn_stats_in_conv and accumulate_dgrad and os.environ.get("SLAK_BLOCK_RUNNER", "1") != "0")
+    """SLAK_BLOCK_RUNNER=0 keeps the Python sequence.  (The kernel switches are not asked: the runner follows slak_tri_plan and slak_mlp_plan under the
+    same `allow` masks as the Python sequence, and declines a block whose plan names a rung it does not issue.)"""
+    return os.environ.get("SLAK_BLOCK_RUNNER", "1") != "0"
 
 
 def _runner():
@@ -1566,10 +1558,11 @@ class _BlockFn(torch.autograd.Function):
                 w1b, bb1b, w2b, bb2b = lowp_param(w1), lowp_param(bb1), lowp_param(w2), lowp_param(bb2)
             group = _bn3_group(bns[0])                                # SyncBatchNorm: the runner calls back for the two statistics exchanges
             exchange = _runner_exchange(group)
-            ctx.mlp_allow = _mlp_allow(w1b, bb1b, w2b, bb2b)         # the backward asks for the same plan
+            ctx.mlp_allow = _mlp_allow(w1b, bb1b, w2b, bb2b)         # the backward asks for the same plans
+            tri_allow = _tri_allow(wv, wh, ws, 2)
             res = R.block_forward(x, x_lowp, wv, wh, ws, [g1, g2, g3], [b1, b2, b3], [bn.running_mean for bn in bns], [bn.running_var for bn in bns],
                                   float(bns[0].eps), float(bns[0].momentum), True, lnw, lnb, float(eps), w1b, bb1b, w2b, bb2b,
-                                  gamma, sample_scale, bool(emit), exchange, int(ldc), ctx.mlp_allow)
+                                  gamma, sample_scale, bool(emit), exchange, int(ldc), ctx.mlp_allow, tri_allow)
             if res:                                                   # (empty: the shape has no one-launch path -- the Python sequence knows the fallbacks)
                 out, out16, x16, yv, yh, ys, bnstats, s, t, mean, rstd, y1m, a, z, count_dev = res
                 pool = getattr(bns[0], "_slak_ctr_pool", None)
@@ -1582,14 +1575,14 @@ class _BlockFn(torch.autograd.Function):
                 else:
                     wts = (lowp_param_t(w1), lowp_param_t(w2)) if cache_lowp_weights else (None, None)
                 ctx.save_for_backward(x16, wv, wh, ws, yv, yh, ys, g1, g2, g3, bnstats, s, lnw, mean, rstd, t, w1b, y1m, a, w2b, z, gamma, sample_scale, *wts)
-                ctx.misc = (True, group, float(x.shape[0] * x.shape[2] * x.shape[3]), count_dev, x.dtype, x_lowp is not None)
+                ctx.misc = (tri_allow, group, float(x.shape[0] * x.shape[2] * x.shape[3]), count_dev, x.dtype, x_lowp is not None)
                 ctx.runner = True
                 ctx.params = (wv, wh, ws, g1, b1, g2, b2, g3, b3, lnw, lnb, w1, bb1, w2, bb2, gamma)
                 ctx.set_materialize_grads(False)
                 return (out, out16) if emit else out
         x16 = x_lowp if x_lowp is not None else x.to(torch.bfloat16)
         x16 = x16.contiguous()
-        yv, yh, ys, st, tri_dgrad = _tri_forward_impl(x16, wv, wh, ws, 2)
+        yv, yh, ys, st, tri_allow = _tri_forward_impl(x16, wv, wh, ws, 2)
         group = _bn3_group(bns[0])
         pre = _bn3_pre_rows(_stats_triple(st, x.device), x16.shape[1]) if st is not None else None
         s, bnstats, count, count_dev = _bn3_forward_impl(yv, yh, ys, [g1, g2, g3], [b1, b2, b3], bns, group, pre)
@@ -1610,14 +1603,14 @@ class _BlockFn(torch.autograd.Function):
         else:
             wts = (lowp_param_t(w1), lowp_param_t(w2)) if cache_lowp_weights else (None, None)
         ctx.save_for_backward(x16, wv, wh, ws, yv, yh, ys, g1, g2, g3, bnstats, s, lnw, mean, rstd, *saved, z, gamma, sample_scale, *wts)
-        ctx.misc = (tri_dgrad, group, count, count_dev, x.dtype, x_lowp is not None)
+        ctx.misc = (tri_allow, group, count, count_dev, x.dtype, x_lowp is not None)
         ctx.set_materialize_grads(False)
         return (out, out16) if emit else out
 
     @staticmethod
     def backward(ctx, dout, dout16=None):
         (x16, wv, wh, ws, yv, yh, ys, g1, g2, g3, bnstats, s, lnw, mean, rstd, t, w1b, y1m, a, w2b, z, gamma, sample_scale, w1t, w2t) = ctx.saved_tensors
-        tri_dgrad, group, count, count_dev, xdtype, had_lowp = ctx.misc
+        tri_allow, group, count, count_dev, xdtype, had_lowp = ctx.misc
         if ctx.runner:
             exchange = _runner_exchange(group)
             w1p = None                                                # stage 1: W1^T in fragment order for the launch that also produces dt
@@ -1626,7 +1619,7 @@ class _BlockFn(torch.autograd.Function):
             res = _runner_mod.block_backward(
                 x16, wv, wh, ws, yv, yh, ys, [g1, g2, g3], bnstats, s, lnw, mean, rstd, t, w1b, y1m, a, w2b, z, gamma, sample_scale, dout, dout16,
                 xdtype == torch.bfloat16, had_lowp, count_dev, exchange, _runner_trace, w1t, w2t, w1p, _grad_destinations(ctx.params), int(w1b.shape[1]),
-                ctx.mlp_allow, _bn_bwd_async)
+                ctx.mlp_allow, tri_allow, _bn_bwd_async)
             return (*res, None, None)                                 # dx, dx_lowp, then the sixteen parameter gradients in forward()'s order
         saved = (t, w1b, y1m, a, w2b)
         dshortcut, dz, dgamma, dzc = _scale_residual_bwd(z, gamma, sample_scale, xdtype, dout, dout16)
@@ -1638,7 +1631,7 @@ class _BlockFn(torch.autograd.Function):
             wg["dw1"], wg["dw2"] = _mlp_bwd_weights(saved, dz, dy1)
         d1, d2, d3, dgam, dbet = _bn3_backward_impl(ds, yv, yh, ys, [g1, g2, g3], bnstats, group, count, count_dev, between=weights)
         need = ctx.needs_input_grad
-        dx16, dwv, dwh, dws = _tri_backward_impl(x16, wv, wh, ws, d1, d2, d3, tri_dgrad, need[0] or need[1], need[2:5])
+        dx16, dwv, dwh, dws = _tri_backward_impl(x16, wv, wh, ws, d1, d2, d3, tri_allow, need[0] or need[1], need[2:5])
         if ctx.pitch is not None:
             wg["dw1"], db1, wg["dw2"] = _cut_pitched_grads(ctx.pitch[0], wg["dw1"], db1, wg["dw2"])
         dx = dxl = None

@@ -3,8 +3,8 @@
 // pwconv2 -> gamma * + permute + residual, and its backward) as TWO host calls per block and step instead of ~70 ctypes calls, ~25 torch.empty
 // and 4-6 GEMM dispatches made from Python.  Same launches on the same operands in the same order as the Python node: results are bit-identical
 // (tests/test_model_reference_gpu.py::test_block_runner_issues_the_same_launches_as_the_python_node).  Host-only C++ on the C ABI of include/slak_hip.h; tensors are allocated through the torch allocator, kernels
-// go to torch's CURRENT stream, the GEMMs the library does not cover are at::linear / at::mm (hipBLASLt).  Which launch runs each step of the pointwise MLP
-// is the library's answer (slak_mlp_plan under the caller's `allow` mask): the Python sequence switches on the same plan.
+// go to torch's CURRENT stream, the GEMMs the library does not cover are at::linear / at::mm (hipBLASLt).  Which launch runs each step of the branch convs and
+// of the pointwise MLP is the library's answer (slak_tri_plan, slak_mlp_plan under the caller's `allow` masks): the Python sequence switches on the same plans.
 //
 // SyncBatchNorm (round 5): with an `exchange` callable (block_ops._sync_bn_all_reduce bound to the process group) the branch BatchNorms run as
 // sums -> exchange -> apply: forward one blocking all-reduce of 6C+1 doubles, backward one all-reduce of 4C floats issued ASYNCHRONOUSLY in front of
@@ -19,8 +19,9 @@
 // the backward cuts dW1, db1, dW2 back to the parameters' shapes.  The launches are those of the Python sequence on the same operands: bit-identical results
 // (tests/test_pitched_runner_gpu.py).  ldc == C is the plain block, launch for launch what it was.
 //
-// block_forward returns an EMPTY list when a precondition of the one-launch path does not hold for the shape (no three-branch forward with
-// statistics / data gradient / weight gradient launch): the caller (block_ops._BlockFn) then runs the Python sequence, which knows every fallback.
+// block_forward returns an EMPTY list when slak_tri_plan names a rung that is not issued here (anything but the three-branch forward with statistics
+// and either the one-launch backward or the three-branch data-gradient and weight-gradient launches): the caller (block_ops._BlockFn) then runs the
+// Python sequence, which knows every rung.
 #include <torch/extension.h>
 #include <torch/csrc/distributed/c10d/ProcessGroup.hpp>
 #include <torch/csrc/distributed/c10d/Types.hpp>
@@ -120,33 +121,32 @@ Side& side_of(int dev) {
 
 struct Shape { int N, C, H, W, K, P, M, C4, Cp; };                  // Cp: the row pitch of the NHWC tensors (== C: a plain block); C4: rows of W1 as handed in (4 Cp)
 
-// what the library answers for a block shape and the caller's `allow` mask of MLP kernel families (slak_mlp_plan), asked once
-struct Plan { bool ok; int rows; size_t ws; bool bwd1; slak_mlp_plan_t mlp; size_t off[5], len[5]; };   // off/len: the backward's deferred-reduction regions behind the common scratch
-const Plan& plan_of(const Shape& s, unsigned allow) {
+// what the library answers for a block shape and the caller's `allow` masks (slak_mlp_plan's kernel families, slak_tri_plan's launches), asked once
+struct Plan { bool ok; size_t ws; slak_tri_plan_t tri; slak_mlp_plan_t mlp; size_t off[5], len[5]; };   // off/len: the backward's deferred-reduction regions behind the common scratch
+const Plan& plan_of(const Shape& s, unsigned allow, unsigned tri_allow) {
     static std::map<std::vector<int>, Plan> cache;
-    const std::vector<int> key = {s.N, s.C, s.H, s.W, s.K, s.C4, s.Cp, (int)allow};
+    const std::vector<int> key = {s.N, s.C, s.H, s.W, s.K, s.C4, s.Cp, (int)allow, (int)tri_allow};
     std::lock_guard<std::mutex> lk(g_cache_mu);
     auto it = cache.find(key);
     if (it != cache.end()) return it->second;
     Plan p{};
-    const int dt = SLAK_BF16;
-    p.rows = slak_dwconv2d_tri_stats_rows(dt, s.N, s.C, s.H, s.W, s.K);
-    const size_t wtri = slak_dwconv2d_tri_filter_workspace_bytes(dt, s.N, s.C, s.H, s.W, s.K);
-    p.ok = slak_dwconv2d_tri_supported_op(dt, s.N, s.C, s.H, s.W, s.K, 0) == 1 && slak_dwconv2d_tri_supported_op(dt, s.N, s.C, s.H, s.W, s.K, 1) == 1 &&
-           p.rows > 0 && wtri > 0 && slak_mlp_plan(s.M, s.C4, s.Cp, allow, &p.mlp) == SLAK_OK;
+    // (dgrad == ONE is taken without asking slak_dwconv2d_tri_supported_op(.., 1), which the runner used to require of every block: the one-launch
+    // backward exists only inside the small three-branch class, where that query says yes)
+    p.ok = slak_tri_plan(SLAK_BF16, s.N, s.C, s.H, s.W, s.K, tri_allow, &p.tri) == SLAK_OK && p.tri.fwd == SLAK_TRI_FWD_TRI_STATS &&
+           (p.tri.dgrad == SLAK_TRI_DGRAD_ONE || (p.tri.dgrad == SLAK_TRI_DGRAD_TRI && p.tri.wgrad == SLAK_TRI_WGRAD_TRI)) &&
+           slak_mlp_plan(s.M, s.C4, s.Cp, allow, &p.mlp) == SLAK_OK;
     if (s.Cp == s.C) p.ok = p.ok && (s.C % 2) == 0 && s.C <= 1024;
     else {                                                         // pitched: any parity of C; every tail op must have a kernel for (C, ldc)
         p.ok = p.ok && s.Cp > s.C && s.Cp % 8 == 0 && s.Cp <= 1024 && s.C4 == 4 * s.Cp;
         for (int op = SLAK_TAIL_LN_FWD; op <= SLAK_TAIL_SR_BWD; ++op)
             for (int sdt : {SLAK_F32, SLAK_BF16}) p.ok = p.ok && slak_block_tail_family(op, sdt, s.N, s.C, s.P, s.Cp) != SLAK_TAIL_FAMILY_NONE;
     }
-    p.bwd1 = slak_dwconv2d_tri_backward_supported(dt, s.N, s.C, s.H, s.W, s.K) == 1;
     // backward: the five calls whose final column sums are deferred into one launch keep their partial rows until then: a region each,
     // behind the scratch the other calls share -- [scale_residual][gelu'][LayerNorm][dW1][dW2]
     const auto up = [](size_t v) { return (v + 255) / 256 * 256; };
     const size_t tail = slak_block_tail_workspace_bytes(s.N, s.Cp, s.P);
     const size_t len[5] = {tail, p.mlp.ws_dy1, tail, p.mlp.ws_dw1, p.mlp.ws_dw2};
-    size_t o = up(std::max({wtri, slak_bn3_workspace_bytes(s.N, s.C), tail, p.mlp.ws_dy1, p.mlp.ws_dw1, p.mlp.ws_dw2}));   // (the MLP launches use their regions; leaving them out here moves the regions and made the step time bimodal: profiles/mlp_plan_step_times.jsonl)
+    size_t o = up(std::max({p.tri.ws_wgrad, slak_bn3_workspace_bytes(s.N, s.C), tail, p.mlp.ws_dy1, p.mlp.ws_dw1, p.mlp.ws_dw2}));   // (the MLP launches use their regions; leaving them out here moves the regions and made the step time bimodal: profiles/mlp_plan_step_times.jsonl)
     for (int k = 0; k < 5; ++k) { p.off[k] = o; p.len[k] = up(std::max<size_t>(len[k], 256)); o += p.len[k]; }
     p.ws = o;
     return cache.emplace(key, p).first->second;
@@ -170,14 +170,15 @@ std::vector<Tensor> block_forward(const Tensor& x, const c10::optional<Tensor>& 
                                   const Tensor& bb2b, const Tensor& gamma, const c10::optional<Tensor>& sample_scale, bool emit_lowp,
                                   const pybind11::object& exchange_obj /* None: single process; else see Exchange */,
                                   int64_t ldc /* row pitch of the NHWC tensors; != C: w1b .. bb2b are the zero-padded operands */,
-                                  int64_t allow /* SLAK_MLP_ALLOW_*: block_ops' use_skinny_linear / use_linear_gemm / use_linear_wgrad */) {
+                                  int64_t allow /* SLAK_MLP_ALLOW_*: block_ops' use_skinny_linear / use_linear_gemm / use_linear_wgrad */,
+                                  int64_t tri_allow /* SLAK_TRI_ALLOW_*: block_ops._tri_allow */) {
     Exchange exchange(exchange_obj);
     TORCH_CHECK(w1b.dim() == 2 && w2b.dim() == 2 && ldc == w1b.size(1) && ldc == w2b.size(0) && w2b.size(1) == w1b.size(0) && bb1b.numel() == w1b.size(0) &&
                 bb2b.numel() == ldc, "the pointwise operands do not fit the pitch");
     TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 4, "x must be a contiguous (N,C,H,W) HIP tensor");
     TORCH_CHECK(bn_gamma.size() == 3 && bn_beta.size() == 3 && bn_mean.size() == 3 && bn_var.size() == 3, "three branch BatchNorms");
     const Shape s = shape_of(x, wv, w1b);
-    const Plan& pl = plan_of(s, (unsigned)allow);
+    const Plan& pl = plan_of(s, (unsigned)allow, (unsigned)tri_allow);
     const bool f32w = wv.scalar_type() == at::kFloat && wh.scalar_type() == at::kFloat && wsm.scalar_type() == at::kFloat && wv.is_contiguous() &&
                       wh.is_contiguous() && wsm.is_contiguous() && wv.size(3) == 5 && wh.size(2) == 5 && wh.size(3) == s.K && wsm.size(2) == 5 && wsm.size(3) == 5;
     if (!pl.ok || !f32w || (x.scalar_type() != at::kFloat && x.scalar_type() != at::kBFloat16) || w1b.scalar_type() != at::kBFloat16) return {};
@@ -188,7 +189,7 @@ std::vector<Tensor> block_forward(const Tensor& x, const c10::optional<Tensor>& 
     const Scratch ws = scratch(x, pl.ws);
     // three branch convs + the BatchNorms' batch sums
     Tensor yv = at::empty_like(x16), yh = at::empty_like(x16), ys = at::empty_like(x16);
-    Tensor stats = at::empty({pl.rows, s.C, 6}, x.options().dtype(at::kFloat));
+    Tensor stats = at::empty({pl.tri.stats_rows, s.C, 6}, x.options().dtype(at::kFloat));
     check_rc(slak_dwconv2d_tri_forward_stats(x16.data_ptr(), fp(wv), fp(wh), fp(wsm), yv.data_ptr(), yh.data_ptr(), ys.data_ptr(), fpm(stats), dt,
                                              s.N, s.C, s.H, s.W, s.K, st), "slak_dwconv2d_tri_forward_stats");
     // branch BatchNorms + add
@@ -197,7 +198,7 @@ std::vector<Tensor> block_forward(const Tensor& x, const c10::optional<Tensor>& 
     float* rm[3] = {fpm(bn_mean[0]), fpm(bn_mean[1]), fpm(bn_mean[2])};
     float* rv[3] = {fpm(bn_var[0]), fpm(bn_var[1]), fpm(bn_var[2])};
     const float* pre[3] = {fp(stats), fp(stats) + 2, fp(stats) + 4};
-    const int pre_rows[3] = {pl.rows, pl.rows, pl.rows};
+    const int pre_rows[3] = {pl.tri.stats_rows, pl.tri.stats_rows, pl.tri.stats_rows};
     Tensor coef = at::empty({s.C * 4}, stats.options()), bnstats = at::empty({s.C * 6}, stats.options());
     Tensor sum = at::empty_like(yv), count_dev;
     if (exchange.none()) {
@@ -309,7 +310,7 @@ std::vector<Tensor> block_backward(const Tensor& x16, const Tensor& wv, const Te
                                    const c10::optional<Tensor>& count_dev, const pybind11::object& exchange_obj, const pybind11::object& trace,
                                    const c10::optional<Tensor>& w1t_opt, const c10::optional<Tensor>& w2t_opt /* cached transposed bf16 weights, or None */,
                                    const c10::optional<Tensor>& w1p_opt /* W1^T in fragment-major order (slak_linear_nt_gelu_bwd_dt), or None */,
-                                   const std::vector<c10::optional<Tensor>>& grad_dst, int64_t ldc, int64_t allow /* as in block_forward */,
+                                   const std::vector<c10::optional<Tensor>>& grad_dst, int64_t ldc, int64_t allow, int64_t tri_allow /* as in block_forward */,
                                    bool bn_bwd_async /* block_ops._bn_bwd_async: the backward statistics exchange on the collective's own stream */) {
     Exchange exchange(exchange_obj);
     const Shape s = shape_of(x16, wv, w1b);
@@ -319,8 +320,8 @@ std::vector<Tensor> block_backward(const Tensor& x16, const Tensor& wv, const Te
     const GradDst gd{grad_dst.empty() ? nullptr : &grad_dst, (int)x16.get_device()};
     const GradDst gdm = pitched ? GradDst{nullptr, (int)x16.get_device()} : gd;       // dW1, db1, dW2 of a pitched block come out padded and are cut at the end
     enum { G_WV, G_WH, G_WS, G_G1, G_B1, G_G2, G_B2, G_G3, G_B3, G_LNW, G_LNB, G_W1, G_BB1, G_W2, G_BB2, G_GAMMA };
-    const Plan& pl = plan_of(s, (unsigned)allow);
-    TORCH_CHECK(pl.ok, "block_backward: the shape has no one-launch path (block_forward would have declined it)");
+    const Plan& pl = plan_of(s, (unsigned)allow, (unsigned)tri_allow);
+    TORCH_CHECK(pl.ok, "block_backward: slak_tri_plan names a rung that is not issued here (block_forward would have declined the block)");
     c10::hip::HIPGuard guard(x16.get_device());
     void* st = stream_of(x16);
     const int dt = SLAK_BF16;
@@ -453,7 +454,7 @@ std::vector<Tensor> block_backward(const Tensor& x16, const Tensor& wv, const Te
     // three branch convs: the summed data gradient, the three weight gradients
     Tensor dx16 = at::empty_like(x16);
     Tensor dwv = gd.take(G_WV, wv.sizes(), f32), dwh = gd.take(G_WH, wh.sizes(), f32), dws = gd.take(G_WS, wsm.sizes(), f32);
-    if (pl.bwd1) {                                                 // 14 x 14 class: data gradient and the three weight gradients in one launch
+    if (pl.tri.dgrad == SLAK_TRI_DGRAD_ONE) {                      // 14 x 14 class: data gradient and the three weight gradients in one launch
         check_rc(slak_dwconv2d_tri_backward(d1.data_ptr(), d2.data_ptr(), d3.data_ptr(), x16.data_ptr(), fp(wv), fp(wh), fp(wsm), dx16.data_ptr(),
                                             fpm(dwv), fpm(dwh), fpm(dws), dt, s.N, s.C, s.H, s.W, s.K, ws.p, ws.n, st), "slak_dwconv2d_tri_backward");
     } else {

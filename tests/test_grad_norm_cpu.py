@@ -33,7 +33,7 @@ def test_new_entries_check_their_arguments():
     assert L.slak_adamw_step_scaled(p, p, hyp, -2, p, None) == INVALID
     assert L.slak_adamw_step_scaled(p, p, hyp, _lib.ADAMW_MAX_GROUPS + 1, p, None) == INVALID
     assert L.slak_adamw_step_scaled(p, p, hyp, 1, None, None) == INVALID
-    assert L.slak_version() == 9                                     # no existing entry changed its argument list
+    assert L.slak_version() == 10                                    # no existing entry changed its argument list (10: slak_tri_plan added)
 
 
 def test_fused_step_has_no_cpu_fallback():

@@ -228,3 +228,117 @@ def test_block_runner_and_python_node_follow_the_same_mlp_plan(case, gpu):
     assert np.array_equal(y0, y1) and np.array_equal(dx0, dx1)
     bad = [n for n in g0 if not np.array_equal(g0[n], g1[n])]
     assert set(g0) == set(g1) and not bad, bad
+
+
+# (x shape, kernel_size, the block_ops switch turned off | None) -> the rungs of slak_tri_plan the case is there for (fwd, dgrad, wgrad), and whether the
+# C++ runner takes the block.  Width 64 keeps the MLP on its LIBRARY rungs throughout.  (PAIR needs a library switch, a process of its own:
+# tests/test_ab_switches_gpu.py runs the pair entry under SLAK_TRI_ROWS=0 / SLAK_TRI_WAVE=0.)
+TRI_RUNG_CASES = {
+    "p8_one_launch": ((2, 64, 8, 8), (13, 5), None, ("tri_stats", "one", "one"), True),
+    "p8_two_launches": ((2, 64, 8, 8), (13, 5), "fused_tri_backward", ("tri_stats", "tri", "tri"), True),
+    "p8_branch_wgrad": ((2, 64, 8, 8), (13, 5), "fused_tri_wgrad", ("tri_stats", "tri", "branch"), False),
+    "p28_no_stats": ((2, 64, 28, 28), (13, 5), "bn_stats_in_conv", ("tri", "tri", "tri"), False),
+    "p34x64_branch": ((2, 64, 34, 64), (31, 5), None, ("branch_stats", "branch_acc", "tri"), False),
+    "p34x64_branch_add": ((2, 64, 34, 64), (31, 5), "accumulate_dgrad", ("branch_stats", "branch_add", "tri"), False),
+}
+_TRI_SWITCH_BITS = {"fused_tri_backward": "TRI_ALLOW_BACKWARD", "fused_tri_wgrad": "TRI_ALLOW_WGRAD", "bn_stats_in_conv": "TRI_ALLOW_STATS",
+                    "accumulate_dgrad": "TRI_ALLOW_DGRAD_ACC"}
+_tri_default_runs = {}
+
+
+def _tri_block_run(shape, ks, gpu, use_runner, switch=None):
+    """One block forward + backward -> (y, x.grad, {parameter: gradient}, {buffer: value}, did the runner take the block); `switch`: the block_ops
+    switch that is off during the run, use_runner False: the Python sequence."""
+    from slak_amd import block_ops
+    import slak_amd.slak_model as M
+    _set_fused(True, True)
+    saved = block_ops._runner_mod
+    if not use_runner:
+        block_ops._runner_mod = None
+    saved_switch = getattr(block_ops, switch) if switch is not None else None
+    if switch is not None:
+        setattr(block_ops, switch, False)
+    try:
+        torch.manual_seed(7)
+        blk = M.Block(shape[1], drop_path=0.0, layer_scale_init_value=0.5, kernel_size=ks, Decom=True, bn=True, lowp_dwconv=True).to(gpu)
+        blk.train()
+        x = torch.randn(*shape, device=gpu, requires_grad=True)
+        with torch.autocast("cuda", dtype=torch.bfloat16):
+            y = blk(x)
+        assert type(y.grad_fn).__name__ == "_BlockFnBackward"
+        took = y.grad_fn.runner
+        y.float().pow(2).mean().backward()
+        return (y.detach().double().cpu().numpy(), x.grad.double().cpu().numpy(), {n: p.grad.double().cpu().numpy() for n, p in blk.named_parameters()},
+                {n: b.double().cpu().numpy() for n, b in blk.named_buffers()}, took)
+    finally:
+        if switch is not None:
+            setattr(block_ops, switch, saved_switch)
+        block_ops._runner_mod = saved
+        _set_fused(False)
+
+
+def _tri_default_run(shape, ks, gpu):
+    """The Python sequence at the default switches: computed once per shape, shared by the cases, never written to."""
+    if (shape, ks) not in _tri_default_runs:
+        _tri_default_runs[(shape, ks)] = _tri_block_run(shape, ks, gpu, False)
+    return _tri_default_runs[(shape, ks)]
+
+
+def _same_bits(a, b, what):
+    (ya, dxa, ga, ba, _), (yb, dxb, gb, bb, _) = a, b
+    assert np.array_equal(ya, yb) and np.array_equal(dxa, dxb), what
+    bad = [n for n in ga if not np.array_equal(ga[n], gb[n])] + [n for n in ba if not np.array_equal(ba[n], bb[n])]
+    assert set(ga) == set(gb) and set(ba) == set(bb) and not bad, (what, bad)
+
+
+@pytest.mark.parametrize("case", list(TRI_RUNG_CASES))
+def test_block_runner_and_python_node_follow_the_same_tri_plan(case, gpu):
+    """Both callers of slak_tri_plan on one block per rung of the branch convs' ladder, with the block_ops switch of the case flipped at run time.  Each
+    case first asserts that the plan of its shape and mask names the rungs it is there for and that the runner takes or declines the block as the
+    plan dictates.  Where the runner takes the block: output, x.grad, every parameter gradient and the running statistics bit-identical between the
+    C++ runner and the Python sequence.  Against the Python sequence at the default switches:
+      * the data gradient and the weight gradients in two launches: the same bits (include/slak_hip.h promises them for slak_dwconv2d_tri_backward);
+      * per-branch weight gradients: everything but the three filter gradients has the same bits; those are fp32 sums of N H W = 128 products in
+        another order, each within test_fused_launches_gpu's _check_dw bound (1e-5 of the largest gradient at this length) of the exact sum, so
+        within twice that of each other;
+      * BatchNorm sums from the statistics kernel's own pass instead of the conv launch: other fp32 partial sums, so bf16 roundings flip from the
+        BatchNorm output on -- every result within the 1e-2 per bf16 op that this file holds the model to;
+      * per-branch data gradients added as tensors instead of in the copy-out: the same bits (ops.dwconv2d_backward_data_accumulate is a tensor add of
+        the gradient, bit for bit: tests/test_mfma_gpu.py::test_backward_data_accumulate_is_a_tensor_add_of_the_gradient)."""
+    import ctypes
+    from slak_amd import _lib, block_ops
+    if block_ops._runner() is None:
+        pytest.skip("block runner module not built")
+    shape, ks, switch, rungs, takes = TRI_RUNG_CASES[case]
+    allow = _lib.TRI_ALLOW_ALL & ~(getattr(_lib, _TRI_SWITCH_BITS[switch]) if switch else 0)
+    plan = _lib.TriPlan()
+    assert _lib.lib().slak_tri_plan(_lib.SLAK_BF16, *shape, ks[0], allow, ctypes.byref(plan)) == 0
+    assert (_lib.TRI_FWD_NAMES[plan.fwd], _lib.TRI_DGRAD_NAMES[plan.dgrad], _lib.TRI_WGRAD_NAMES[plan.wgrad]) == rungs
+    assert takes == (plan.fwd == _lib.TRI_FWD_TRI_STATS and (plan.dgrad == _lib.TRI_DGRAD_ONE or
+                                                              (plan.dgrad, plan.wgrad) == (_lib.TRI_DGRAD_TRI, _lib.TRI_WGRAD_TRI)))
+    with_runner = _tri_block_run(shape, ks, gpu, True, switch)
+    python = _tri_block_run(shape, ks, gpu, False, switch) if switch else _tri_default_run(shape, ks, gpu)
+    assert with_runner[4] is takes and python[4] is False
+    _same_bits(with_runner, python, "C++ runner (or the Python sequence behind a runner that declined) against the Python sequence")
+    if switch is None:
+        return
+    default = _tri_default_run(shape, ks, gpu)
+    y, dx, grads, bufs, _ = python
+    y0, dx0, grads0, bufs0, _ = default
+    if switch == "fused_tri_backward":
+        _same_bits(python, default, "two launches against one")
+    elif switch == "accumulate_dgrad":
+        _same_bits(python, default, "tensor adds against the accumulating copy-out")
+    elif switch == "fused_tri_wgrad":
+        filters = [n for n in grads if grads[n].ndim == 4]
+        assert len(filters) == 3 and np.array_equal(y, y0) and np.array_equal(dx, dx0) and all(np.array_equal(bufs[n], bufs0[n]) for n in bufs)
+        assert all(np.array_equal(grads[n], grads0[n]) for n in grads if n not in filters)
+        for n in filters:
+            err = np.abs(grads[n] - grads0[n]).max()
+            print(case, n, "max difference %.3e, largest gradient %.3e" % (err, np.abs(grads0[n]).max()))
+            assert err <= 2 * 1e-5 * max(1.0, np.abs(grads0[n]).max()), (n, err)
+    else:
+        assert switch == "bn_stats_in_conv"
+        figures = [("y", _rel(y, y0)), ("x.grad", _rel(dx, dx0))] + [(n, _rel(grads[n], grads0[n])) for n in grads] + [(n, _rel(bufs[n], bufs0[n])) for n in bufs]
+        print(case, sorted(figures, key=lambda f: -f[1])[:6])
+        assert max(f for _, f in figures) <= 1e-2, sorted(figures, key=lambda f: -f[1])[:5]

@@ -6,6 +6,7 @@
     python tools/print_dispatch.py --queries OUT.npz  the support / size queries (host code only, no GPU needed) over QUERY_GRID, and over the stage
                                                       shapes with each switch of QUERY_SWITCHES off -> tests/golden/dispatch_queries.npz
     python tools/print_dispatch.py --mlp              slak_mlp_plan for the pointwise MLP of every stage of the configurations (host code only)
+    python tools/print_dispatch.py --tri              slak_tri_plan for the three branch convs of every stage of the configurations (host code only)
     python tools/print_dispatch.py --stage-queries    (what --queries runs in a child process per switch: switches are read once per process)
     python tools/print_dispatch.py --switches OUT.json  the launches of the small shapes (--small) in one child process per conv A/B switch
                                                       of tests/ab_switches.py's SWITCHES, the switch at its flip value: per switch the keys whose family differs from
@@ -180,9 +181,24 @@ def mlp_plans():
     return out
 
 
+def tri_plans():
+    """{stage: {step: rung}}: slak_tri_plan (allow = every launch, bf16) for the three branch convs of every stage of CONFIGS.  Host code only."""
+    lib = _load("slak_amd/_lib.py", "_slak_lib_only")
+    L, out = lib.lib(), {}
+    for cfg, (N, stages) in CONFIGS.items():
+        for si, (C, HW, K) in enumerate(stages):
+            p = lib.TriPlan()
+            lib.check(L.slak_tri_plan(BF16, N, C, HW, HW, K, lib.TRI_ALLOW_ALL, ctypes.byref(p)), "slak_tri_plan")
+            out["%s/s%d" % (cfg, si + 1)] = {"fwd": lib.TRI_FWD_NAMES[p.fwd], "stats_rows": p.stats_rows, "dgrad": lib.TRI_DGRAD_NAMES[p.dgrad],
+                                             "wgrad": lib.TRI_WGRAD_NAMES[p.wgrad], "ws_wgrad": p.ws_wgrad}
+    return out
+
+
 if __name__ == "__main__":
     if "--mlp" in sys.argv:
         print(json.dumps(mlp_plans(), indent=0))
+    elif "--tri" in sys.argv:
+        print(json.dumps(tri_plans(), indent=0))
     elif "--switches" in sys.argv:
         switch_tables(sys.argv[sys.argv.index("--switches") + 1])
     elif "--stage-queries" in sys.argv:
